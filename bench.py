@@ -6,15 +6,25 @@ One "step" = one full FD step of BASELINE config 3 per GPU:
   -> [all-gather rewards] -> fdr_fd_weights -> fdr_fd_grad -> [RCCL all-reduce of g] -> fdr_dsgd_step.
 Per-GPU work is fixed as N grows ("weak" scaling): the global batch is 4096 * N perturbations.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does what the headline figure needs: set up, W warmup steps (+ the clock settle), K timed steps, one
+JSON line.  `--full` adds everything else the benchmark reports: the cpu_baseline leg, the rollout-timing pass
+(HIP events) with the roofline figures derived from it, and the 4096-pair variant of config 3.
+
+The timed steps always start from the same state, whatever ran before them: after warmup and settle, theta, the
+noise-index stream, the step seeds (and config 5's omega / archive) are put back to their values at set-up and
+one untimed step re-primes the index prefetch.  `--dump-outputs DIR` writes what the last timed step handed its
+caller (the batch's per-lane returns / entropies / norms, the gradient, the updated theta, the update norms) as
+DIR/<name>.npy, so two builds can be compared output for output.
 
 `--gpus N > 1` without an external launcher (no WORLD_SIZE in the environment) starts the N ranks itself: the
 parent never touches the GPU, runs `torch.distributed.run --nproc-per-node N` as a child, relays its output and
 checks that rank 0's line reports N GPUs.  Under an external launcher `--gpus` must equal WORLD_SIZE, and N must
 not exceed the visible devices: either mismatch exits non-zero before any GPU work.
 
-Prints ONE JSON line on rank 0.  The cpu_baseline leg (rank 0, N = 1) times the oracle's
+Prints ONE JSON line on rank 0.  The cpu_baseline leg (`--full`, rank 0, N = 1) times the oracle's
 reference-shaped per-lane CPU loop (torch CPU forward per step, as worker/agent.py does) on a
 bounded sample, BEFORE the GPU is initialised.
 """
@@ -166,7 +176,7 @@ def bench_trap(args):
     per epoch + the device learner) on cuda:0.  A step is one train epoch."""
     import numpy as np
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import torch
         torch.set_num_threads(1)
         from oracle import runner as orun
@@ -201,8 +211,12 @@ def bench_trap(args):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     steps = runner.agent.cumulative_timesteps - s0
+    if args.dump_outputs:
+        last = runner.history[-1] if runner.history else {}
+        dump_outputs(args.dump_outputs, {"reward": last.get("rewards"), "update": last.get("Update Magnitude"),
+                                         "theta": runner.policy.get_trainable_flat()})
     line = {"metric": METRIC, "value": round(steps / el, 1), "unit": "env steps/s", "n_gpus": 1, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 4),
+            "warmup": args.warmup, "full": args.full, "ms_per_step": round(el / args.steps * 1e3, 4),
             "sec_per_fd_step": round(el / args.steps, 6), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "BASELINE config 1: run_sequential.py SequentialRunner on custom_envs.simple_trap_env "
@@ -216,6 +230,29 @@ def bench_trap(args):
 
 
 # ------------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays {name: array-like or None} -> path/<name>.npy, float32 kept, everything else as float64.  An array
+    over its share of DUMP_MAX_BYTES is cut to a fixed seeded sample of its elements (flattened, in index order)."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items() if v is not None}
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def _host(t):
+    return None if t is None else t.detach().cpu().numpy()
+
+
 def check_devices(n):
     """Exit non-zero unless n GPUs are visible.  torch.cuda.device_count() counts devices without starting the
     HIP runtime on this image, so the self-launching parent stays GPU-free."""
@@ -274,20 +311,27 @@ def main():
                     help="antithetic lanes per GPU (default: the BASELINE config's -- 4096 halfcheetah, "
                          "1024 cartpole, 1024 x 4 envs impala)")
     ap.add_argument("--episode-len", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the cpu_baseline leg, the rollout-timing "
+                         "pass with the roofline figures, the 4096-pair variant (config 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variant", action="store_true", help="skip the 4096-pair variant line (config 3)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-variant", action="store_true", help="--full without the 4096-pair variant line (config 3)")
     ap.add_argument("--settle-ms", type=float, default=100.0,
                     help="after the W warmup steps, further untimed FD steps until this much wall time has passed "
                          "since the first warmup step: the GPU's clocks ramp over the first ~30 ms of sustained load "
                          "(config 3 rollout 1.24 -> 1.06 ms over its first 25 launches, rocprofv3 trace, DESIGN.md 7); "
                          "0 disables")
     ap.add_argument("--timing-steps", type=int, default=10,
-                    help="FD steps of the rollout-timing pass that follows the timed region (HIP events around "
+                    help="--full: FD steps of the rollout-timing pass that follows the timed region (HIP events around "
                          "each rollout; Impala: the in-rollout conv/core phase events)")
     ap.add_argument("--no-novelty", action="store_true", help="config 5 without the novelty archive / omega "
                     "(rocprof passes: the archive's conv launches would mix into the rollout conv's average)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1 (got %d)" % args.steps)
     rehearse = os.environ.get("FDR_BENCH_REHEARSE") == "1"
     ext_world = os.environ.get("WORLD_SIZE")
     if ext_world is None:
@@ -316,7 +360,7 @@ def main():
     L = args.perturbations or (IMPALA_LANES if kind == "impala" else DEFAULT_LANES.get(args.config, 4096))
     E = IMPALA_ENVS if kind == "impala" else 1
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import impala as oimp
         from oracle import policies as opol
         P = oimp.num_params(n_act) if kind == "impala" else opol.num_params(kind, n_in, n_act)
@@ -413,6 +457,7 @@ def main():
     torch.cuda.synchronize()
     cur = [None]
     host_ms = [None]  # the timed loop's host enqueue time per step (before the closing synchronize)
+    last = [None]     # the FDBatch of the last step of the latest timed_loop
 
     def fd_step(timed, n_dirs=n_dirs_global, rng=lane_range):
         timed = timed and cur[0] is not None
@@ -432,6 +477,33 @@ def main():
             phase_ms.append(engine.impala_profile_read())
         return out, batch
 
+    # Everything a step's outputs depend on besides its arguments: theta, the index stream, the step seed, and with
+    # novelty omega (-> the DSGD step scale) and the archive.  The learner's history / epoch and the agent's step
+    # count change too, but no output of a current-epoch batch reads them.
+    def snapshot():
+        s = {"theta": policy.flat.detach().clone(), "mt_key": table._mt_key.copy(), "mt_pos": table._mt_pos.value,
+             "ahead": table._ahead.copy(), "omega": (omega.omega, list(omega.reward_history))}
+        if novelty:
+            s["archive"] = (list(handler.points), None if handler.archive is None else handler.archive.clone(),
+                            None if handler.pair is None else handler.pair.copy(), handler.worst_point_idx)
+        return s
+
+    def restore(s):
+        policy.flat.copy_(s["theta"])
+        table._mt_key[:] = s["mt_key"]
+        table._mt_pos.value = s["mt_pos"]
+        table._ahead = s["ahead"].copy()
+        worker._next = None          # indices drawn ahead of the old stream position
+        omega.omega, omega.reward_history = s["omega"][0], list(s["omega"][1])
+        if novelty:
+            pts, arch, pair, worst = s["archive"]
+            handler.points = list(pts)
+            if arch is not None:
+                handler.archive.copy_(arch)
+            handler.pair = None if pair is None else pair.copy()
+            handler.worst_point_idx = worst
+        step_no[0] = 0
+
     def timed_loop(steps, events=False, **kw):
         # events=False: the timed region carries no instrumentation (an event record on the stream costs
         # ~5 us of barrier processing at each kernel boundary it sits on: rocprofv3 trace);
@@ -447,10 +519,10 @@ def main():
             prof.enable()
         t0 = time.perf_counter()
         pairs = []
-        out = None
+        out = batch = None
         for i in range(steps):
             cur[0] = ev_pool[i % len(ev_pool)] if events else None
-            out, _ = fd_step(True, **kw)
+            out, batch = fd_step(True, **kw)
             if cur[0] is not None:
                 pairs.append(cur[0])
         t_host = time.perf_counter() - t0
@@ -465,8 +537,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
+        last[0] = batch
         return el, [a_.elapsed_time(b_) for a_, b_ in pairs], out
 
+    start = snapshot()
     t_warm = time.perf_counter()
     for _ in range(args.warmup):
         out, _ = fd_step(False)
@@ -485,14 +559,27 @@ def main():
         for _ in range(5):
             out, _ = fd_step(False)
         settle_steps += 5
+    # the timed steps start from the set-up state however many steps ran above (their number depends on the
+    # clock); one untimed step from there uploads the next step's indices ahead, as every later step does
+    with torch.no_grad():
+        restore(start)
+    out, _ = fd_step(False)
     elapsed, _, out = timed_loop(args.steps)
     host_enqueue_ms = host_ms[0]
-    # rollout-timing pass (outside the timed region): HIP events bracketing each rollout on its stream,
+    if args.dump_outputs and rank == 0:
+        b = last[0]
+        dump_outputs(args.dump_outputs, {
+            "reward": _host(b.reward), "entropy": _host(b.entropy), "timesteps": _host(b.timesteps),
+            "norm2": _host(b.norm2), "novelty": _host(b.novelty), "grad": _host(learner.gradient_memory),
+            "theta": _host(policy.flat), "update": _host(out)})
+    # rollout-timing pass (--full, outside the timed region): HIP events bracketing each rollout on its stream,
     # and for Impala the per-step-loop phase events of fdr_impala_profile
-    if impala:
+    roll_ms = [0.0]
+    if args.full and impala:
         engine.impala_profile(True)
-    _, roll_ms, _ = timed_loop(max(1, min(args.steps, args.timing_steps)), events=True)
-    if impala:
+    if args.full:
+        _, roll_ms, _ = timed_loop(max(1, min(args.steps, args.timing_steps)), events=True)
+    if args.full and impala:
         engine.impala_profile(False)
     rollout_ms = float(np.mean(roll_ms))
     if world > 1:
@@ -502,12 +589,12 @@ def main():
     upd, gnorm = out.tolist()
     assert gnorm > 0 and np.isfinite(upd)
     conv_phase = None
-    if impala:
+    if args.full and impala:
         conv_phase = [float(np.mean([p[i] for p in phase_ms])) for i in range(3)]
         phase_ms.clear()
 
     variants = {}
-    if not impala and args.config == "halfcheetah" and not args.no_variant:
+    if args.full and not impala and args.config == "halfcheetah" and not args.no_variant:
         # also report the 4096-pair variant (4096 directions x +-, 8192 lanes per GPU)
         nv = 2 * n_dirs_global
         rng2 = fdist.lane_range(nv, 2, world, rank)
@@ -533,11 +620,12 @@ def main():
     value = lane_steps / elapsed
     prof = None
     pmc = os.path.join(REPO, "profiles", "pmc_rollout_%s.json" % args.config)
-    if os.path.exists(pmc):
+    if args.full and os.path.exists(pmc):
         with open(pmc) as f:
             prof = json.load(f)
     traffic = None if prof is None else prof.get("hbm_bytes_per_launch")
-    if impala:
+    roofline = None    # --full: derived from the rollout-timing pass
+    if args.full and impala:
         conv_ms, core_ms, replay_ms = conv_phase
         if world > 1:
             t = torch.tensor([conv_ms, core_ms, replay_ms], dtype=torch.float64, device=dev)
@@ -571,14 +659,15 @@ def main():
                     "note": ("dense f16 MFMA peak" if fp16 else "f32 MFMA peak (= f32 vector peak)") +
                             "; conv time from HIP events between the step-loop launches (fdr_impala_profile); "
                             "traffic / mfma_busy_pmc: rocprofv3 PMC of the same command (profile)"}
+    if impala:
         workload = ("BASELINE config %d per GPU: ImpalaPolicy(A=%d) P=%d, %d perturbations (%d directions x +/-) x "
                     "%d envs each, synthetic 3x64x64 frames, T=%d, %s, full FD step (rollout + entropy pass + "
                     "weights + gradient + DSGD%s)" % (5 if fp16 else 4, n_act, policy.num_params, L, L // 2, E, T,
                                                       "fp16 rollouts" if fp16 else "f32",
                                                       " + lane novelty vs a TVD strategy archive over %d zeta obs + "
                                                       "AdaptiveOmega step" % ZETA_SIZE if novelty else ""))
-    else:
-        flops = lane_step_flops(kind, n_in, n_act) * L * T
+    if args.full and not impala:
+        flops =lane_step_flops(kind, n_in, n_act) * L * T
         achieved_tf = flops / (rollout_ms * 1e-3) / 1e12
         hbm = None
         if traffic:
@@ -596,6 +685,7 @@ def main():
                             "for the whole episode, so the kernel is VALU-issue bound; its HBM traffic (PMC "
                             "FETCH_SIZE x2 + WRITE_SIZE of the same kernel, 'profile') is the noise-table gather once "
                             "per episode"}
+    if not impala:
         workload = ("BASELINE config 3: HalfCheetah-shaped synthetic env (obs 17, act 6), MujocoPolicy(17,6) P=%d, "
                     "%d antithetic perturbations per GPU (%d directions x +/-), T=%d fixed-length episodes, full FD "
                     "step (rollout + weights + gradient + DSGD)" % (policy.num_params, L, L // 2, T)
@@ -609,7 +699,7 @@ def main():
         "unit": "env steps/s",
         "n_gpus": world,
         "steps": args.steps,
-        "warmup": args.warmup, "settle_steps": settle_steps,
+        "warmup": args.warmup, "settle_steps": settle_steps, "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "sec_per_fd_step": round(elapsed / args.steps, 6),
         # the timed loop's host time per step before its closing synchronize; the upload ring bounds the host's lead

@@ -9,7 +9,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
   for lib in ${LIBS:-libfdr}; do
     for c in ${CONFIGS:-halfcheetah}; do
       log=gpurun_out/abb_${lib}_${c}_$r.log
-      FDR_LIB=$PWD/dfd-starter_amd/fdr/$lib.so timeout -k 10 300 python bench.py --config $c --no-cpu-baseline \
+      FDR_LIB=$PWD/dfd-starter_amd/fdr/$lib.so timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline \
         --no-variant ${BENCH_ARGS:-} > $log 2>&1; rc=$?
       if [ $rc -ne 0 ] || grep -qE "$FAULT" $log; then echo "$lib $c FAIL rc=$rc"; tail -5 $log; exit 3; fi
       python - "$lib" "$c" "$log" <<'PY'

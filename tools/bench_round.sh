@@ -13,7 +13,7 @@ b() {  # b <config> <timeout> <args...>
   if grep -qE "$FAULT" "gpurun_out/bench_${TAG}_${cfg}.log"; then echo "GPU FAULT"; exit 3; fi
   [ "$rc" -eq 0 ] || exit "$rc"
 }
-b halfcheetah 300 ${BENCH_ARGS:-}
-b cartpole 300
-b impala 400 --steps 5 --warmup 1
-b impala_fp16 300 --steps 5 --warmup 1
+b halfcheetah 300 --full ${BENCH_ARGS:-}
+b cartpole 300 --full
+b impala 400 --full --steps 5 --warmup 1
+b impala_fp16 300 --full --steps 5 --warmup 1

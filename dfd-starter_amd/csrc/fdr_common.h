@@ -13,14 +13,18 @@ constexpr int kHidden = 64;  // policies/discrete.py:35-36, policies/mujoco.py:3
 // ---------------------------------------------------------------------------------------------
 // Counter random stream (oracle/rng.py restates it for the checker; DESIGN.md "Random streams")
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
+// mix64 in its three rounds and hash_ctr's counter word, separately callable: the pair rollout kernel spreads one
+// draw batch over the steps of the batch before it (mix64 = c(b(a(z))), hash_ctr = mix64(hash_ctr_word))
+__host__ __device__ __forceinline__ uint64_t mix64_a(uint64_t z) { return (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; }
+__host__ __device__ __forceinline__ uint64_t mix64_b(uint64_t z) { return (z ^ (z >> 27)) * 0x94D049BB133111EBull; }
+__host__ __device__ __forceinline__ uint64_t mix64_c(uint64_t z) { return z ^ (z >> 31); }
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) { return mix64_c(mix64_b(mix64_a(z))); }
+__device__ __forceinline__ uint64_t hash_ctr_word(uint64_t key, uint64_t lane, uint64_t t, uint64_t k) {
+  const uint64_t c = (lane << 32) | (t << 4) | k;
+  return key + c * 0x9E3779B97F4A7C15ull;
 }
 __device__ __forceinline__ uint64_t hash_ctr(uint64_t key, uint64_t lane, uint64_t t, uint64_t k) {
-  const uint64_t c = (lane << 32) | (t << 4) | k;
-  return mix64(key + c * 0x9E3779B97F4A7C15ull);
+  return mix64(hash_ctr_word(key, lane, t, k));
 }
 constexpr uint64_t kJiggleT = (1ull << 28) - 1;
 
@@ -29,12 +33,13 @@ __device__ __forceinline__ float uniform24(uint64_t h) {
 }
 // Box-Muller on the hardware transcendental units: v_log_f32 is log2, v_cos_f32 takes revolutions,
 // so cos(2*pi*u2) needs no range reduction.  Agrees with oracle/rng.py to a few ulp.
-__device__ __forceinline__ float normal_bm(uint64_t h) {
-  const float u1 = (float)((uint32_t)(h >> 40) + 1u) * 0x1p-24f;
-  const float u2 = (float)((uint32_t)(h >> 16) & 0xFFFFFFu) * 0x1p-24f;
-  const float r = __builtin_sqrtf(-1.38629436111989061f * __builtin_amdgcn_logf(u1));  // -2 ln u1
-  return r * __builtin_amdgcn_cosf(u2);
+__device__ __forceinline__ float bm_u1(uint64_t h) { return (float)((uint32_t)(h >> 40) + 1u) * 0x1p-24f; }
+__device__ __forceinline__ float bm_u2(uint64_t h) { return (float)((uint32_t)(h >> 16) & 0xFFFFFFu) * 0x1p-24f; }
+__device__ __forceinline__ float bm_radius(float u1) {
+  return __builtin_sqrtf(-1.38629436111989061f * __builtin_amdgcn_logf(u1));  // -2 ln u1
 }
+__device__ __forceinline__ float bm_normal(float r, float u2) { return r * __builtin_amdgcn_cosf(u2); }
+__device__ __forceinline__ float normal_bm(uint64_t h) { return bm_normal(bm_radius(bm_u1(h)), bm_u2(h)); }
 
 // tanh(x) = 1 - 2 / (1 + e^{2x}) on v_exp_f32 / v_rcp_f32 (abs error ~3e-7; saturates to +-1)
 constexpr float kTanhScale = 2.88539008177792681f;  // 2 * log2(e)

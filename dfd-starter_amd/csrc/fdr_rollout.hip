@@ -1142,19 +1142,47 @@ struct MlpPair {
     }
   }
 
-  // Layer 1 (units 2t, 2t+1) and the env's M[t] . s in one pass over the broadcast input chunks.
-  template <bool kSameInput>
-  __device__ __forceinline__ f2 layer1_env(const float* xs, const float* ss, const L1Rows& rows, float& env) const {
+  // The env state chunks layer 1 read (the input itself when kSameInput), kept for env_ms
+  struct SIn {
+    float4 v[NQ];
+    float t;
+  };
+  // Layer 1 (units 2t, 2t+1) over the broadcast input chunks; the env state chunks go to `sin`.  The chunk reads
+  // are issued first and `fill` (work that needs none of them) runs while they are in flight.
+  template <bool kSameInput, class Fill>
+  __device__ __forceinline__ f2 layer1_env(const float* xs, const float* ss, const L1Rows& rows, SIn& sin,
+                                           Fill&& fill) const {
     const float4* x4 = reinterpret_cast<const float4*>(xs);
     const float4* s4 = reinterpret_cast<const float4*>(ss);
-    return layer1_env_q<kSameInput>([&](int q) { return x4[q]; }, [&](int q) { return s4[q]; }, rows, env,
-                                    kTail ? xs[4 * NQ] : 0.f, kTail ? ss[4 * NQ] : 0.f);
+    SIn xin;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      xin.v[q] = x4[q];
+      sin.v[q] = kSameInput ? xin.v[q] : s4[q];
+    }
+    xin.t = kTail ? xs[4 * NQ] : 0.f;
+    sin.t = kSameInput ? xin.t : (kTail ? ss[4 * NQ] : 0.f);
+    fill();
+    __builtin_amdgcn_sched_barrier(0);  // layer 1 (asm statements: no class mask holds them) stays behind the fill
+    return layer1_q(xin, rows);
   }
-  template <bool kSameInput, class XQ, class SQ>
-  __device__ __forceinline__ f2 layer1_env_q(XQ&& xq, SQ&& sq, const L1Rows& rows, float& env, float xt,
-                                             float st) const {
-    f2 aa0 = {b1a, 0.f}, aa1 = {0.f, 0.f}, ab0 = {b1b, 0.f}, ab1 = {0.f, 0.f};
+  // M[t] . s from the chunks layer 1 read (no part of the policy's chain: the compiler interleaves it with layer 1)
+  __device__ __forceinline__ float env_ms(const SIn& sin, const L1Rows& rows) const {
     f2 am0 = {0.f, 0.f}, am1 = {0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const float4 sv = sin.v[q], mv = rows.m[q];
+      am0 = pk_fma(f2{mv.x, mv.y}, f2{sv.x, sv.y}, am0);
+      am1 = pk_fma(f2{mv.z, mv.w}, f2{sv.z, sv.w}, am1);
+    }
+    if constexpr (kTail) am1.x = fmaf(rows.tm, sin.t, am1.x);
+    const f2 am = am0 + am1;
+    return am.x + am.y;
+  }
+  __device__ __forceinline__ f2 layer1_q(const SIn& xin, const L1Rows& rows) const {
+    const float xt = xin.t;
+    auto xq = [&](int q) { return xin.v[q]; };
+    f2 aa0 = {b1a, 0.f}, aa1 = {0.f, 0.f}, ab0 = {b1b, 0.f}, ab1 = {0.f, 0.f};
     if constexpr (kPk) {
       // units (a, b) packed: acc[k % NC] += (w_a(k), w_b(k)) * x_k; the bias column (k = NIN) is added.
       // NC = 2 chains of ~9 dependent packed FMAs
@@ -1164,8 +1192,7 @@ struct MlpPair {
       for (int q = 0; q < NC; ++q) acc[q] = f2{0.f, 0.f};
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
-        const float4 xv = xq(q), mv = rows.m[q];
-        const float4 sv = kSameInput ? xv : sq(q);
+        const float4 xv = xq(q);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int k = 4 * q + i;
@@ -1182,21 +1209,16 @@ struct MlpPair {
               acc[k % NC] = (k & 1) ? pk_fma_bhi(f2{w.z, w.w}, xp, acc[k % NC]) : pk_fma_blo(f2{w.x, w.y}, xp, acc[k % NC]);
           }
         }
-        am0 = pk_fma(f2{mv.x, mv.y}, f2{sv.x, sv.y}, am0);
-        am1 = pk_fma(f2{mv.z, mv.w}, f2{sv.z, sv.w}, am1);
       }
       if constexpr (kTail) {  // input 4 NQ = NIN - 1, then the bias
         const float4 w = rows.wp[(NIN - 1) >> 1];
         acc[(NIN - 1) % NC] = pk_fma(((NIN - 1) & 1) ? f2{w.z, w.w} : f2{w.x, w.y}, f2{xt, xt}, acc[(NIN - 1) % NC]);
-        am1.x = fmaf(rows.tm, kSameInput ? xt : st, am1.x);
       }
       if constexpr (!kPre || NIN % NC >= NIN) {
         const float4 w = rows.wp[NIN >> 1];
         acc[NIN % NC] = acc[NIN % NC] + ((NIN & 1) ? f2{w.z, w.w} : f2{w.x, w.y});
       }
       const f2 h = acc[0] + acc[1];
-      const f2 am = am0 + am1;
-      env = am.x + am.y;
       if constexpr (DISC) {
         return f2{act1(h.x, a1a, c1a), act1(h.y, a1b, c1b)};
       } else {
@@ -1205,8 +1227,7 @@ struct MlpPair {
     }
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const float4 xv = xq(q), mv = rows.m[q];
-      const float4 sv = kSameInput ? xv : sq(q);
+      const float4 xv = xq(q);
       float4 wa, wb;
       if constexpr (kW1Lds) {
         wa = rows.wa[q];
@@ -1217,18 +1238,14 @@ struct MlpPair {
       }
       aa0 = pk_fma(f2{wa.x, wa.y}, f2{xv.x, xv.y}, aa0);
       ab0 = pk_fma(f2{wb.x, wb.y}, f2{xv.x, xv.y}, ab0);
-      am0 = pk_fma(f2{mv.x, mv.y}, f2{sv.x, sv.y}, am0);
       aa1 = pk_fma(f2{wa.z, wa.w}, f2{xv.z, xv.w}, aa1);
       ab1 = pk_fma(f2{wb.z, wb.w}, f2{xv.z, xv.w}, ab1);
-      am1 = pk_fma(f2{mv.z, mv.w}, f2{sv.z, sv.w}, am1);
     }
-    if constexpr (kTail) {  // w x + b of the last chunk, and m s
+    if constexpr (kTail) {  // w x + b of the last chunk
       aa1 = pk_fma(f2{rows.ta.x, rows.ta.y}, f2{xt, 1.f}, aa1);
       ab1 = pk_fma(f2{rows.tb.x, rows.tb.y}, f2{xt, 1.f}, ab1);
-      am1.x = fmaf(rows.tm, kSameInput ? xt : st, am1.x);
     }
-    const f2 am = am0 + am1, ha = aa0 + aa1, hb = ab0 + ab1;
-    env = am.x + am.y;
+    const f2 ha = aa0 + aa1, hb = ab0 + ab1;
     if constexpr (DISC) {
       return f2{act1(ha.x + ha.y, a1a, c1a), act1(hb.x + hb.y, a1b, c1b)};
     } else {
@@ -1238,11 +1255,14 @@ struct MlpPair {
 
   // Layer 2 and the head: h1 = this thread's layer-1 units (2t, 2t+1); h1s = the half's scratch.
   // Returns the head pre-activation for output o = t & 15 (identical in both rows of the half).
+  // Wave priority: low for the 64 independent layer-2 FMAs (from the h1 write on), raised for the serial part of the
+  // step -- reduce-scatter, tanh, head, action, env, x hand-off, layer 1 -- so the SIMD's other wave yields to it
   template <class Mark>
   __device__ __forceinline__ float layers23(f2 h1, float* h1s, int t, Mark&& mark) const {
     const int c4 = t & 3;
     float x[16];
     reinterpret_cast<f2*>(h1s)[t] = h1;
+    __builtin_amdgcn_s_setprio(0);
     wave_lds_sync();
     lds_bcast<16>(h1s + 16 * c4, x);
     float w3[32];
@@ -1351,6 +1371,7 @@ struct MlpPair {
     // reduce-scatter over the quad: slot i = acc[i / 2][i % 2]; level 1 o_i = v_i + partner(c ^ 2).v_{i + 4} in
     // the order o2, o3, o0, o1, level 2 o_i += partner(c ^ 1).o_{i + 2} -- every DPP source >= 3 instructions old
     f2 zs;
+    __builtin_amdgcn_s_setprio(1);
     {
       float o0, o1, o2, o3;
       asm volatile(
@@ -1509,7 +1530,33 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
     const uint64_t hsh = hash_ctr(key, ulane, (uint64_t)(st + ds), (uint64_t)dk);
     rbuf = DISC ? uniform24(hsh) : normal_bm(hsh);
   };
-  auto step = [&](int st, int tb) {
+  // continuous: the batch after the running one is drawn in five parts, each in the x hand-off of one step of the
+  // running batch -- its first four and its last (draw(st) = parts 0 .. 4 in order; the state between parts is dz,
+  // then du1 / du2)
+  int dctr = ((t / kDrawsPerStep) << 4) | (t % kDrawsPerStep);  // counter word bits of (step offset, dim)
+  uint64_t dz = 0;
+  float du1 = 0.f, du2 = 0.f;
+  auto draw_part = [&](int k, int st) {
+    if (k == 0) {
+      asm volatile("" : "+v"(dctr)::"memory");
+      dz = mix64_a(key + (((uint64_t)ulane << 32) | (uint64_t)((st << 4) + dctr)) * 0x9E3779B97F4A7C15ull);
+    } else if (k == 1) {
+      asm volatile("" : "+v"(dz)::"memory");
+      dz = mix64_b(dz);
+    } else if (k == 2) {
+      asm volatile("" : "+v"(dz)::"memory");
+      const uint64_t hsh = mix64_c(dz);
+      du1 = bm_u1(hsh);
+      du2 = bm_u2(hsh);
+    } else if (k == 3) {
+      asm volatile("" : "+v"(du1)::"memory");
+      du1 = bm_radius(du1);
+    } else if (k == 4) {
+      asm volatile("" : "+v"(du1), "+v"(du2)::"memory");
+      rbuf = bm_normal(du1, du2);
+    }
+  };
+  auto step = [&](int st, int tb, auto&& fill) {
     // this step's draw: the uniform (discrete) or the normal of action dim o (continuous)
     const float zt = __builtin_bit_cast(
         float, __builtin_amdgcn_ds_bpermute(zbase + 4 * kDrawsPerStep * tb, __builtin_bit_cast(int, rbuf)));
@@ -1520,7 +1567,9 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
     xs[t] = t < NIN ? policy_input(s) : (t == NIN ? 1.f : 0.f);
     if constexpr (!kSame) h1s[t] = t < NIN ? s : 0.f;
     wave_lds_sync();
-    const f2 h1 = pl.template layer1_env<kSame>(xs, h1s, l1rows, pre);
+    typename Lane::SIn sin;
+    const f2 h1 = pl.template layer1_env<kSame>(xs, h1s, l1rows, sin, fill);
+    pre = pl.env_ms(sin, l1rows);
 
     mark(0, h1.x);
     const float y = pl.layers23(h1, h1s, t, mark);
@@ -1585,29 +1634,33 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
   };
   if constexpr (!DISC) {
     [&] {
-      // continuous: the loop unrolled by the draw batch (5 steps for 6 dims); the draw is issued
-      // unconditionally at the top of the unrolled body (det lanes ignore it), so it schedules into the
-      // first step's waits instead of sitting behind a branch
+      // continuous: the loop unrolled by the draw batch (5 steps for 6 dims); batch 0 is drawn here, every later
+      // batch unconditionally during the batch before it (det lanes ignore the draws; the one drawn for steps >= T
+      // is never used)
       int st = 0;
+      draw(0);
       for (; st + kStepsPerBatch <= T; st += kStepsPerBatch) {
         asm volatile("" ::: "memory");
         mark(-1, s);
-        draw(st);
 #pragma unroll
         for (int k = 0; k < kStepsPerBatch; ++k) {
           if (k) {
             asm volatile("" ::: "memory");
             mark(-1, s);
           }
-          if (step(st + k, k)) return;  // kTerm: both halves done
+          // parts 0 - 3 in the batch's first four steps; part 4 writes rbuf, so it goes into the batch's last step,
+          // after that step's zt -- rbuf's last read -- is taken
+          constexpr int kLast = kStepsPerBatch - 1;
+          static_assert(kLast >= 4, "draw_part: five parts need a batch of five steps");
+          const int part = k == kLast ? 4 : (k < 4 ? k : -1);
+          if (step(st + k, k, [&] { draw_part(part, st + kStepsPerBatch); })) return;  // kTerm: both halves done
         }
       }
-      if (st < T) {
-        draw(st);
+      if (st < T) {  // the remainder's draws are the batch drawn ahead
         for (int k = 0; st + k < T; ++k) {
           asm volatile("" ::: "memory");
           mark(-1, s);
-          if (step(st + k, k)) return;
+          if (step(st + k, k, [] {})) return;
         }
       }
     }();
@@ -1616,7 +1669,7 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
       asm volatile("" ::: "memory");
       mark(-1, s);
       if (!det && tb == 0) draw(st);
-      if (step(st, tb)) break;
+      if (step(st, tb, [] {})) break;
       tb = tb + 1 == kStepsPerBatch ? 0 : tb + 1;
     }
   }

@@ -242,6 +242,22 @@ int fdr_policy_forward(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_la
                                (hipStream_t)stream);
 }
 
+int fdr_diag_theta_prime(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_lanes_desc* lanes, int32_t n_lanes,
+                         int32_t loader, float* out, int32_t* reads, int32_t* counted, double* n2, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  PolicyKey k;
+  int rc = policy_key(policy, &k);
+  if (rc) return rc;
+  LanesArgs la;
+  rc = lanes_args(lanes, n_lanes, k.n_params, &la);
+  if (rc) return rc;
+  if (loader != FDR_LOADER_LANE && loader != FDR_LOADER_PAIR) return set_error(FDR_ERR_INVALID, "unknown loader");
+  if (!out || !reads || !counted || !n2) return set_error(FDR_ERR_INVALID, "NULL output");
+  if (n_lanes == 0) return FDR_OK;
+  return launch_theta_prime(k, la, n_lanes, loader, policy->bn_mean, policy->bn_var, out, reads, counted, n2,
+                            (hipStream_t)stream);
+}
+
 int fdr_rollout(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_desc* env,
                 const fdr_lanes_desc* lanes, int32_t n_lanes, uint64_t seed, int32_t jiggle,
                 const float* obs_mean, const float* obs_std, double* ret, double* ent,

@@ -110,4 +110,37 @@ struct ParamSrc {
   }
 };
 
+// Diagnostics (fdr_diag_theta_prime): a ParamSrc that also records what the loaders ask of it.  Every accessor returns
+// ParamSrc's own value and stores it at out[p], adds 1 to reads[p], and to counted[p] when the call is one that
+// contributes to n2 (get, and get_if with `use`).  The three rows are this lane's; rec = false records nothing (the
+// idle half of a pair wave, which shadows its partner).  Plain vector stores and int atomics.
+struct RecordSrc : ParamSrc {
+  float* out;
+  int32_t* reads;
+  int32_t* counted;
+  bool rec;
+
+  __device__ __forceinline__ void note(int64_t p, float v, bool cnt) const {
+    if (!rec) return;
+    out[p] = v;
+    atomicAdd(&reads[p], 1);
+    if (cnt) atomicAdd(&counted[p], 1);
+  }
+  __device__ __forceinline__ float get(int64_t p) {
+    const float v = ParamSrc::get(p);
+    note(p, v, true);
+    return v;
+  }
+  __device__ __forceinline__ float get_if(int64_t p, bool use) {
+    const float v = ParamSrc::get_if(p, use);
+    note(p, v, use);
+    return v;
+  }
+  __device__ __forceinline__ float get_nocount(int64_t p) const {
+    const float v = ParamSrc::get_nocount(p);
+    note(p, v, false);
+    return v;
+  }
+};
+
 }  // namespace fdr

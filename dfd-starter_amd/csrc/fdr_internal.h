@@ -107,6 +107,10 @@ int launch_policy_forward(const PolicyKey& k, const LanesArgs& lanes, int n_lane
                           const float* bn_mean, const float* bn_var, const float* x, float* out0,
                           float* out1, hipStream_t stream);
 int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream);
+// fdr_diag_theta_prime: what MlpLane::load / MlpPair::load read through a RecordSrc (out / reads / counted [n_lanes, P])
+int launch_theta_prime(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, int loader, const float* bn_mean,
+                       const float* bn_var, float* out, int32_t* reads, int32_t* counted, double* n2,
+                       hipStream_t stream);
 
 // Delayed-return perturbation rows (fdr_fd_lambda_norms / fdr_fd_grad_lambda), by value to kernels.
 int64_t bn_refresh_workspace_bytes(int n);

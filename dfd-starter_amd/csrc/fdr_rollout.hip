@@ -23,6 +23,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "../../include/fdr_diag.h"
 #include "fdr_common.h"
 #include "fdr_internal.h"
 #include "fdr_wave.h"
@@ -201,7 +202,9 @@ struct MlpLane {
   float b3;
   float a0, c0, a1, c1, a2, c2;  // discrete: folded BN for input j / hidden unit j
 
-  __device__ __forceinline__ void load(ParamSrc& src, int j, const float* bn_mean,
+  // Src: ParamSrc (every rollout / forward kernel), or RecordSrc (the theta' read-back, fdr_diag_theta_prime)
+  template <class Src>
+  __device__ __forceinline__ void load(Src& src, int j, const float* bn_mean,
                                        const float* bn_var, float4* lds_tile) {
     const int r = j >> 3, c = j & 7, o = j & 15, q = j >> 4;
     tile = lds_tile + j;
@@ -975,7 +978,8 @@ struct MlpPair {
     return 32 * rho + 8 * (k >> 2) + 4 * e + (k & 3);  // thread 4q + c holds units 8q + c, 8q + 4 + c
   }
 
-  __device__ __forceinline__ void load(ParamSrc& src, int t, int tid, const float* bn_mean, const float* bn_var,
+  template <class Src>  // ParamSrc, or RecordSrc (MlpLane::load)
+  __device__ __forceinline__ void load(Src& src, int t, int tid, const float* bn_mean, const float* bn_var,
                                        float4* wave_tile) {
     const int rho = t >> 4, o = t & 15;
     const int ua = 2 * t, ub = 2 * t + 1;
@@ -1818,6 +1822,90 @@ int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const R
   FDR_SHAPES(FDR_ROLL)
 #undef FDR_ROLL
   return set_error(FDR_ERR_UNSUPPORTED, "no compiled rollout for this (kind, n_in, n_act)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Diagnostics: read-back of the theta' the two loaders form (fdr_diag_theta_prime, include/fdr_diag.h)
+// ---------------------------------------------------------------------------------------------
+// Only lanes.src(lane) and the loader's load, under the thread mapping of the kernel that owns the loader
+// (rollout_kernel / rollout_pair_kernel with lane_base 0), over a RecordSrc: out / reads / counted [n_lanes, P] receive
+// every value the loader asked for, n2 [n_lanes] the norm as the rollouts sum it.  No rollout kernel runs this code.
+struct ThetaPrimeArgs {
+  LanesArgs lanes;
+  int n_lanes;
+  int64_t P;
+  const float* bn_mean;
+  const float* bn_var;
+  float* out;
+  int32_t* reads;
+  int32_t* counted;
+  double* n2;
+
+  __device__ __forceinline__ RecordSrc src(int lane, bool rec) const {
+    RecordSrc s;
+    static_cast<ParamSrc&>(s) = lanes.src(lane);
+    s.out = out + (int64_t)lane * P;
+    s.reads = reads + (int64_t)lane * P;
+    s.counted = counted + (int64_t)lane * P;
+    s.rec = rec;
+    return s;
+  }
+};
+
+template <int NIN, int NA, bool DISC>
+__global__ __launch_bounds__(64 * kLanesPerBlock) void theta_prime_lane_kernel(ThetaPrimeArgs a) {
+  using Lane = MlpLane<NIN, NA, DISC>;
+  __shared__ float4 wtile[kLanesPerBlock * Lane::kTileF4];
+  const int j = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = blockIdx.x * kLanesPerBlock + wv;
+  if (lane >= a.n_lanes) return;
+  RecordSrc src = a.src(lane, true);
+  Lane pl;
+  pl.load(src, j, a.bn_mean, a.bn_var, wtile + wv * Lane::kTileF4);
+  const double n2 = wave_sum(src.n2);
+  if (j == 0) a.n2[lane] = n2;
+}
+
+template <int NIN, int NA, bool DISC>
+__global__ __launch_bounds__(64 * kPairWaves) void theta_prime_pair_kernel(ThetaPrimeArgs a) {
+  using Lane = MlpPair<NIN, NA, DISC>;
+  __shared__ float4 wtile[kPairWaves * Lane::kTileF4];
+  const int tid = threadIdx.x & 63, wv = threadIdx.x >> 6, hh = tid >> 5, t = tid & 31;
+  const int lane0 = (blockIdx.x * kPairWaves + wv) * 2;
+  if (lane0 >= a.n_lanes) return;
+  const bool active = lane0 + hh < a.n_lanes;
+  const int lane = active ? lane0 + hh : lane0;  // an idle half shadows its partner, records nothing
+  RecordSrc src = a.src(lane, active);
+  Lane pl;
+  pl.load(src, t, tid, a.bn_mean, a.bn_var, wtile + wv * Lane::kTileF4);
+  double n2 = src.n2;
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) n2 += __shfl_xor(n2, m, kWave);
+  if (t == 0 && active) a.n2[lane] = n2;
+}
+
+int launch_theta_prime(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, int loader, const float* bn_mean,
+                       const float* bn_var, float* out, int32_t* reads, int32_t* counted, double* n2,
+                       hipStream_t stream) {
+  const ThetaPrimeArgs a{lanes, n_lanes, k.n_params, bn_mean, bn_var, out, reads, counted, n2};
+#define FDR_TP(NIN, NA, DISC)                                                                             \
+  if (k.n_in == NIN && k.n_act == NA && k.discrete == DISC) {                                             \
+    if (Layout<NIN, NA, DISC>::P != k.n_params)                                                           \
+      return set_error(FDR_ERR_INVALID, "n_params does not match the policy layout");                     \
+    if (loader == FDR_LOADER_PAIR) {                                                                      \
+      const int quantum = 2 * kPairWaves;                                                                 \
+      hipLaunchKernelGGL((theta_prime_pair_kernel<NIN, NA, DISC>), dim3((n_lanes + quantum - 1) / quantum), \
+                         dim3(64 * kPairWaves), 0, stream, a);                                            \
+      return check_launch("theta_prime_pair_kernel");                                                     \
+    }                                                                                                     \
+    hipLaunchKernelGGL((theta_prime_lane_kernel<NIN, NA, DISC>),                                          \
+                       dim3((n_lanes + kLanesPerBlock - 1) / kLanesPerBlock), dim3(64 * kLanesPerBlock), 0, \
+                       stream, a);                                                                        \
+    return check_launch("theta_prime_lane_kernel");                                                       \
+  }
+  FDR_SHAPES(FDR_TP)
+#undef FDR_TP
+  return set_error(FDR_ERR_UNSUPPORTED, "no compiled loader for this (kind, n_in, n_act)");
 }
 
 }  // namespace fdr

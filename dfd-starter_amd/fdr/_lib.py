@@ -15,6 +15,7 @@ FDR_ENV_SYNTH, FDR_ENV_TRAP = 0, 1
 FDR_DIST_L2, FDR_DIST_TVD, FDR_DIST_W2 = 0, 1, 2
 FDR_ROLLOUT_PAIR, FDR_ROLLOUT_SINGLE, FDR_ROLLOUT_AUTO, FDR_ROLLOUT_WIDE = 0, 1, 2, 3
 FDR_WEIGHT_ZSCORE, FDR_WEIGHT_CENTERED_RANK, FDR_WEIGHT_MOMENTS = 0, 1, 2
+FDR_LOADER_LANE, FDR_LOADER_PAIR = 0, 1   # include/fdr_diag.h
 
 EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy", "fdr_ctx_device",
            "fdr_perturb", "fdr_policy_forward", "fdr_rollout", "fdr_fd_weights",
@@ -33,7 +34,8 @@ EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy",
            "fdr_ctx_set_rollout_impl", "fdr_ctx_set_replay_gemm", "fdr_ctx_impala_profile",
            "fdr_ctx_impala_profile_read", "fdr_ctx_impala_debug_clock", "fdr_noise_draw_indices",
            "fdr_impala_bn_refresh_workspace_bytes", "fdr_impala_bn_refresh", "fdr_atari_strategies_workspace_bytes",
-           "fdr_atari_strategies", "fdr_atari_bn_refresh_workspace_bytes", "fdr_atari_bn_refresh")
+           "fdr_atari_strategies", "fdr_atari_bn_refresh_workspace_bytes", "fdr_atari_bn_refresh",
+           "fdr_diag_theta_prime")
 
 
 class FDRError(RuntimeError):
@@ -93,6 +95,8 @@ def _load():
         "fdr_perturb": (ctypes.c_int, [P, P, I64, P, I64, P, P, I32, F32, P, P]),
         "fdr_policy_forward": (ctypes.c_int, [P, ctypes.POINTER(PolicyDesc), ctypes.POINTER(LanesDesc), I32, P,
                                               P, P, P]),
+        "fdr_diag_theta_prime": (ctypes.c_int, [P, ctypes.POINTER(PolicyDesc), ctypes.POINTER(LanesDesc), I32, I32, P,
+                                                P, P, P, P]),
         "fdr_rollout": (ctypes.c_int, [P, ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc),
                                        ctypes.POINTER(LanesDesc), I32, U64, I32, P, P, P, P, P, P, P]),
         "fdr_rollout_states": (ctypes.c_int, [P, ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc),

@@ -163,6 +163,22 @@ def policy_forward(spec, lanes, n_lanes, x, bn_mean=None, bn_var=None):
     return out0 if out1 is None else (out0, out1)
 
 
+def theta_prime(spec, lanes, n_lanes, loader, bn_mean=None, bn_var=None, device=None):
+    """Diagnostics (include/fdr_diag.h, fdr_diag_theta_prime): the weights one of the MLP rollouts' loaders forms,
+    read back.  loader "lane" | "pair".  -> (out f32, reads i32, counted i32) [n_lanes, P], n2 f64 [n_lanes]."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    _check_dev(bn_mean, bn_var)
+    code = {"lane": _lib.FDR_LOADER_LANE, "pair": _lib.FDR_LOADER_PAIR}[loader]
+    out = torch.full((n_lanes, spec.n_params), float("nan"), dtype=torch.float32, device=dev)
+    reads = torch.zeros((n_lanes, spec.n_params), dtype=torch.int32, device=dev)
+    counted = torch.zeros_like(reads)
+    n2 = torch.full((n_lanes,), -1.0, dtype=torch.float64, device=dev)
+    pd = spec.desc(bn_mean, bn_var)
+    check(lib.fdr_diag_theta_prime(_c(dev), ctypes.byref(pd), ctypes.byref(lanes), n_lanes, code, _p(out), _p(reads),
+                                   _p(counted), _p(n2), _stream(dev)), "fdr_diag_theta_prime")
+    return out, reads, counted, n2
+
+
 class RolloutResult(object):
     """SoA result of one batched rollout (the FDReturn fields, learner/fd_return.py:5-16)."""
 

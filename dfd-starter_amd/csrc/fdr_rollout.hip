@@ -11,7 +11,8 @@
 //   * Activations cross lanes through a 1 KiB per-wave LDS scratch (one ds_write_b32 per lane,
 //     broadcast ds_read_b128 back) feeding packed f32 FMAs, or through DPP row_newbcast where the
 //     input already sits in the caller's 16-lane row (the head, K a).
-//   * The env (synthetic linear-tanh system or the trap gridworld) runs inside the same loop.
+//   * The env (synthetic linear-tanh system, the trap gridworld, or CartPole-v1 / Pendulum-v1 physics) runs inside
+//     the same loop.
 //   * 4 lanes (waves) per 256-thread workgroup, <= 128 VGPRs -> 16 waves/CU: 4096 lanes fill
 //     all 256 CUs in one wave of workgroups.
 #include <hip/hip_runtime.h>
@@ -67,6 +68,49 @@ struct Layout {
 // trap-env observation (environment.py:59-61): python f64 division, cast to f32 by the policy
 __device__ __forceinline__ float trap_obs(int j, int col, int row) {
   return j == 0 ? (float)((double)(col * 7) / 1918.0) : (float)((double)(row * 7) / 1071.0);
+}
+
+// ---- classic-control physics envs (gym classic_control cartpole.py / pendulum.py in f32) ----
+// The state is a few scalars every thread of the wave holds identically (as the trap env's col / row).
+constexpr float kPiF = 3.14159274101257324f;     // fl32(pi)
+constexpr float kTwoPiF = 6.28318548202514648f;  // fl32(2 pi)
+// Reset draw i of a lane: the reserved counter slot t = kJiggleT, k = i (k = 15 there is the jiggle's; action draws
+// have t < 10000), scaled to gym's uniform range as fl32(fl32(scale * u) - shift) -- no contraction: compared bitwise.
+__device__ __forceinline__ float physics_reset(uint64_t key, uint64_t ulane, int i, float scale, float shift) {
+#pragma clang fp contract(off)
+  const float v = scale * uniform24(hash_ctr(key, ulane, kJiggleT, (uint64_t)i));
+  return v - shift;
+}
+// ((th + pi) mod 2 pi) - pi, floor-mod
+__device__ __forceinline__ float wrap_pi(float th) {
+  const float y = th + kPiF;
+  return (y - kTwoPiF * floorf(y * (1.0f / kTwoPiF))) - kPiF;
+}
+// CartPole-v1, explicit Euler (positions advance with the old velocities); returns the failure test of the new state
+__device__ __forceinline__ bool cartpole_step(float& x, float& xd, float& th, float& thd, int act) {
+  const float force = act == 1 ? 10.f : -10.f;
+  const float sn = sinf(th), cs = cosf(th);
+  const float temp = (force + 0.05f * thd * thd * sn) / 1.1f;
+  const float thacc = (9.8f * sn - cs * temp) / (0.5f * (4.0f / 3.0f - 0.1f * cs * cs / 1.1f));
+  const float xacc = temp - 0.05f * thacc * cs / 1.1f;
+  x += 0.02f * xd;
+  xd += 0.02f * xacc;
+  th += 0.02f * thd;
+  thd += 0.02f * thacc;
+  constexpr float kThetaThr = 0.20943951023931953f;  // 12 * 2 pi / 360
+  return x < -2.4f || x > 2.4f || th < -kThetaThr || th > kThetaThr;
+}
+// Pendulum-v1 (g = 10, m = l = 1, dt = 0.05): sn = sin(th) on entry; th is kept wrapped, (cs, sn) follow it.
+// Returns the reward -cost of the pre-step state.
+__device__ __forceinline__ float pendulum_step(float& th, float& thd, float& cs, float& sn, float a) {
+  const float u = fminf(fmaxf(a, -2.f), 2.f);
+  const float w = wrap_pi(th);
+  const float cost = w * w + 0.1f * thd * thd + 0.001f * u * u;
+  thd = fminf(fmaxf(thd + (15.f * sn + 3.f * u) * 0.05f, -8.f), 8.f);
+  th = wrap_pi(th + thd * 0.05f);
+  cs = cosf(th);
+  sn = sinf(th);
+  return -cost;
 }
 
 // torch: two separately rounded tensor ops (utils/torch_helpers.py:25, Normal.sample).
@@ -585,6 +629,9 @@ __global__ __launch_bounds__(64 * kLanesPerBlock) void policy_forward_kernel(
 // bit 4: terminating synthetic env (fdr_env_desc.done_threshold): the lane's episode ends after the step whose
 // next state has |s'[done_dim]| > done_threshold (worker/agent.py:50-52: done -> break), or at T
 // (one lane per wave: the wave leaves its loop -- only these instances carry the test)
+// ENV: FDR_ENV_SYNTH, FDR_ENV_TRAP, or a physics env (FDR_ENV_CARTPOLE at (4, 2, discrete), FDR_ENV_PENDULUM at
+// (3, 1, continuous); !WIDE only) -- per-lane reset states from the counter stream, CartPole's failure test in its
+// own branch (not FEAT bit 4).
 // WIDE (synthetic env, few lanes: <= 2 waves per SIMD): a 256-VGPR budget instead of 128, so the
 // step's loop invariants (M / K rows, the head's W3 slice) stay in registers; the policy input and env
 // state cross lanes by v_readlane instead of an LDS round trip (NIN <= 8); a discrete env's candidate
@@ -643,7 +690,7 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
   float s = 0.f;         // synthetic env state element j (j < NIN)
   if constexpr (ENV == FDR_ENV_SYNTH) {
     s = a.s0[ji];
-  } else {
+  } else if constexpr (ENV == FDR_ENV_TRAP) {
     col = a.trap_start_col;
     row = a.trap_start_row;
     s = trap_obs(j, col, row);
@@ -651,6 +698,29 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
   const int T = a.T;
   const uint64_t key = a.key;
   const uint64_t ulane = (uint64_t)(a.lanes.lane_offset + lane);  // global lane id
+  // physics env state (wave-uniform): CartPole (x, xdot, theta, thetadot); Pendulum (theta, thetadot, cos, sin).
+  // Thread j < NIN selects observation element j into s, so everything downstream of s runs unchanged.
+  float px0 = 0.f, px1 = 0.f, px2 = 0.f, px3 = 0.f;
+  auto physics_obs = [&]() {
+    if constexpr (ENV == FDR_ENV_CARTPOLE) return j == 0 ? px0 : (j == 1 ? px1 : (j == 2 ? px2 : px3));
+    else return j == 0 ? px2 : (j == 1 ? px3 : px1);
+  };
+  (void)physics_obs;
+  if constexpr (ENV == FDR_ENV_CARTPOLE) {  // gym: U(-0.05, 0.05) on all four
+    static_assert(NIN == 4 && NA == 2 && DISC && !WIDE, "CartPole: DiscretePolicy(4, 2), one-lane kernel");
+    px0 = physics_reset(key, ulane, 0, 0.1f, 0.05f);
+    px1 = physics_reset(key, ulane, 1, 0.1f, 0.05f);
+    px2 = physics_reset(key, ulane, 2, 0.1f, 0.05f);
+    px3 = physics_reset(key, ulane, 3, 0.1f, 0.05f);
+    s = physics_obs();
+  } else if constexpr (ENV == FDR_ENV_PENDULUM) {  // gym: theta ~ U(-pi, pi), thetadot ~ U(-1, 1)
+    static_assert(NIN == 3 && NA == 1 && !DISC && !WIDE, "Pendulum: MujocoPolicy(3, 1), one-lane kernel");
+    px0 = physics_reset(key, ulane, 0, kTwoPiF, kPiF);
+    px1 = physics_reset(key, ulane, 1, 2.f, 1.f);
+    px2 = cosf(px0);
+    px3 = sinf(px0);
+    s = physics_obs();
+  }
   constexpr bool kTerm = (FEAT & 16) != 0;
   int nsteps = T;  // env.step calls of the episode (agent.py:47)
   double racc = 0.0;
@@ -875,7 +945,21 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
               return;
             }
           }
+        } else if constexpr (ENV == FDR_ENV_CARTPOLE) {
+          // reward 1 for every step taken, the failing one included; done after it (agent.py:46-52), or at T
+          const bool fail = cartpole_step(px0, px1, px2, px3, act_d);
+          racc += 1.0;
+          s = physics_obs();
+          if (__builtin_amdgcn_readfirstlane(fail ? 1 : 0)) {  // wave-uniform: the whole wave leaves its loop
+            nsteps = t + 1;
+            return;
+          }
+        } else if constexpr (ENV == FDR_ENV_PENDULUM) {
+          // the action (mean, or mean + std z, unscaled) sits in lane 0 of every row
+          racc += (double)pendulum_step(px0, px1, px2, px3, readlane_f(act_c, 0));
+          s = physics_obs();
         } else {
+          static_assert(ENV == FDR_ENV_TRAP, "unknown env kind");
           // custom_envs/simple_trap_env: node.py:9-14, tile_map.py:11-23, environment.py:33-48
           const int prev_x = col * 7;
           const int tc = col + act_d / 3 - 1, tr = row + act_d % 3 - 1;
@@ -1708,6 +1792,10 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
   X(17, 6, false)     \
   X(11, 3, false)     \
   X(8, 2, false)
+// Shapes only the physics envs use (Pendulum's MujocoPolicy(3, 1)): the one-lane rollout of their env, the batched
+// forward and the lane loader's read-back -- no synthetic-env, pair or WIDE instance
+#define FDR_PHYSICS_SHAPES(X) X(3, 1, false)
+static_assert(Layout<3, 1, false>::P == 4546, "MujocoPolicy(3, 1) has 4546 parameters");
 
 int launch_policy_forward(const PolicyKey& k, const LanesArgs& lanes, int n_lanes,
                           const float* bn_mean, const float* bn_var, const float* x, float* out0,
@@ -1722,6 +1810,7 @@ int launch_policy_forward(const PolicyKey& k, const LanesArgs& lanes, int n_lane
     return check_launch("policy_forward_kernel");                                               \
   }
   FDR_SHAPES(FDR_FWD)
+  FDR_PHYSICS_SHAPES(FDR_FWD)
 #undef FDR_FWD
   return set_error(FDR_ERR_UNSUPPORTED, "no compiled policy_forward for this (kind, n_in, n_act)");
 }
@@ -1749,6 +1838,25 @@ static void launch_feat(const RolloutArgs& args, dim3 grid, dim3 block, hipStrea
     FDR_FEAT_CASE(20) FDR_FEAT_CASE(21) FDR_FEAT_CASE(22) FDR_FEAT_CASE(23)
   }
 #undef FDR_FEAT_CASE
+}
+
+// Physics envs (CartPole, Pendulum): the one-lane kernel only, no FEAT bit 4 -- CartPole's termination lives under
+// its ENV branch.  u_inject (bit 3) never comes with the Welford statistics (bit 1): fdr_rollout_ex refuses it.
+template <int NIN, int NA, bool DISC, int ENV>
+static int launch_physics(const PolicyKey& k, const RolloutArgs& args, dim3 grid, dim3 block, hipStream_t stream) {
+  if (Layout<NIN, NA, DISC>::P != k.n_params)
+    return set_error(FDR_ERR_INVALID, "n_params does not match the policy layout");
+  const int feat = (args.states ? 1 : 0) | (args.os_mean ? 2 : 0) | (args.obs_mean ? 4 : 0) | (args.u_inject ? 8 : 0);
+#define FDR_FEAT_CASE(F) \
+  case F: hipLaunchKernelGGL((rollout_kernel<NIN, NA, DISC, ENV, F, false>), grid, block, 0, stream, args); break;
+  switch (feat) {
+    FDR_FEAT_CASE(0) FDR_FEAT_CASE(1) FDR_FEAT_CASE(2) FDR_FEAT_CASE(3)
+    FDR_FEAT_CASE(4) FDR_FEAT_CASE(5) FDR_FEAT_CASE(6) FDR_FEAT_CASE(7)
+    FDR_FEAT_CASE(8) FDR_FEAT_CASE(9) FDR_FEAT_CASE(12) FDR_FEAT_CASE(13)
+    default: return set_error(FDR_ERR_UNSUPPORTED, "u_inject is not combined with the obs statistics");
+  }
+#undef FDR_FEAT_CASE
+  return check_launch(ENV == FDR_ENV_CARTPOLE ? "rollout_kernel<cartpole>" : "rollout_kernel<pendulum>");
 }
 
 // More lanes than one resident round (2 waves per SIMD = 16 lanes per CU) go out as consecutive launches of
@@ -1795,6 +1903,17 @@ static bool use_wide_kernel(const Context& ctx, int n_lanes) {
 
 int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream) {
   const dim3 grid((args.n_lanes + kLanesPerBlock - 1) / kLanesPerBlock), block(64 * kLanesPerBlock);
+  // physics envs: one policy shape each, always rollout_kernel<.., false> whatever the context's rollout_impl says
+  if (env_kind == FDR_ENV_CARTPOLE) {
+    if (k.n_in != 4 || k.n_act != 2 || !k.discrete)
+      return set_error(FDR_ERR_UNSUPPORTED, "CartPole needs a DiscretePolicy(4, 2)");
+    return launch_physics<4, 2, true, FDR_ENV_CARTPOLE>(k, args, grid, block, stream);
+  }
+  if (env_kind == FDR_ENV_PENDULUM) {
+    if (k.n_in != 3 || k.n_act != 1 || k.discrete)
+      return set_error(FDR_ERR_UNSUPPORTED, "Pendulum needs a MujocoPolicy(3, 1)");
+    return launch_physics<3, 1, false, FDR_ENV_PENDULUM>(k, args, grid, block, stream);
+  }
 #define FDR_ROLL(NIN, NA, DISC)                                                                 \
   if (k.n_in == NIN && k.n_act == NA && k.discrete == DISC) {                                   \
     if (Layout<NIN, NA, DISC>::P != k.n_params)                                                 \
@@ -1905,6 +2024,20 @@ int launch_theta_prime(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, 
   }
   FDR_SHAPES(FDR_TP)
 #undef FDR_TP
+  // the physics-only shapes have a lane loader and no pair loader
+#define FDR_TP_LANE(NIN, NA, DISC)                                                                        \
+  if (k.n_in == NIN && k.n_act == NA && k.discrete == DISC) {                                             \
+    if (Layout<NIN, NA, DISC>::P != k.n_params)                                                           \
+      return set_error(FDR_ERR_INVALID, "n_params does not match the policy layout");                     \
+    if (loader != FDR_LOADER_LANE)                                                                        \
+      return set_error(FDR_ERR_UNSUPPORTED, "no pair loader compiled for this (kind, n_in, n_act)");      \
+    hipLaunchKernelGGL((theta_prime_lane_kernel<NIN, NA, DISC>),                                          \
+                       dim3((n_lanes + kLanesPerBlock - 1) / kLanesPerBlock), dim3(64 * kLanesPerBlock), 0, \
+                       stream, a);                                                                        \
+    return check_launch("theta_prime_lane_kernel");                                                       \
+  }
+  FDR_PHYSICS_SHAPES(FDR_TP_LANE)
+#undef FDR_TP_LANE
   return set_error(FDR_ERR_UNSUPPORTED, "no compiled loader for this (kind, n_in, n_act)");
 }
 

@@ -14,6 +14,13 @@ into the rollout kernel, so an env here is a *descriptor*: device tensors + shap
   next state has |s[done_dim]| > done_threshold -- episodes then end before T, per lane (worker/agent.py:50-52).
 * ``TrapEnv`` -- custom_envs/simple_trap_env (environment.py:8-61) on the GPU, integer-exact:
   the reference's walkable bitmap ships as data (custom_envs/simple_trap_env/trap_map.npz).
+* ``CartPoleEnv`` / ``PendulumEnv`` -- gym's classic-control CartPole-v1 and Pendulum-v1 (the published formulas,
+  f32) stepped inside the one-lane rollout kernel.  Every lane resets to its own state, drawn from the
+  counter stream by its global lane id (gym's U(-0.05, 0.05)^4; theta ~ U(-pi, pi), thetadot ~ U(-1, 1)).  CartPole
+  pays 1 per step and ends when |x| > 2.4 or |theta| > 12 degrees, or at the time limit; Pendulum clamps the
+  (unscaled) action to [-2, 2], pays -(theta^2 + 0.1 thetadot^2 + 0.001 u^2) and always runs to the limit.  Pure
+  descriptors: they own no device tensors.  ``make_env(..., physics=True)`` returns them; by default the CartPole /
+  Pendulum ids keep mapping to ``SyntheticEnv`` shapes.
 * ``StackedFrameEnv`` -- the same hash frames as 4 x 84 x 84 stacks for AtariPolicy (fdr_atari_rollout).
 * ``FrameEnv`` -- the Atari/procgen-shaped workload of BASELINE configs 4/5 for ImpalaPolicy:
   uint8-valued 3x64x64 frames from a counter hash of (env, t, pixel), a +1/-1/0 reward for hitting
@@ -97,6 +104,41 @@ class TrapEnv(object):
     def desc(self):
         return _lib.EnvDesc(_lib.FDR_ENV_TRAP, 2, 9, self.episode_len, None, None, None,
                             self.walkable.data_ptr(), self.map_w, self.map_h, 0.0, 0)
+
+
+class _PhysicsEnv(object):
+    """A classic-control env of the rollout kernel: shape, time limit and kind, nothing on the device."""
+    kind = None
+    obs_dim = act_dim = 0
+    discrete = terminates = False
+    ts_limit = 10000    # fdr_env_desc: episode_len 1 .. 10000 (worker/agent.py:12)
+
+    def __init__(self, episode_len):
+        self.episode_len = int(episode_len)
+        if not 1 <= self.episode_len <= self.ts_limit:
+            raise ValueError("episode_len must be in 1 .. %d" % self.ts_limit)
+
+    def desc(self):
+        return _lib.EnvDesc(self.kind, self.obs_dim, self.act_dim, self.episode_len, None, None, None, None, 0, 0,
+                            0.0, 0)
+
+
+class CartPoleEnv(_PhysicsEnv):
+    """gym CartPole-v1 (``episode_len=200``: CartPole-v0), DiscretePolicy(4, 2); episodes end on failure."""
+    kind = _lib.FDR_ENV_CARTPOLE
+    obs_dim, act_dim, discrete, terminates = 4, 2, True, True
+
+    def __init__(self, episode_len=500):
+        super().__init__(episode_len)
+
+
+class PendulumEnv(_PhysicsEnv):
+    """gym Pendulum-v1, MujocoPolicy(3, 1) (obs cos theta, sin theta, thetadot); fixed-length episodes."""
+    kind = _lib.FDR_ENV_PENDULUM
+    obs_dim, act_dim, discrete, terminates = 3, 1, False, False
+
+    def __init__(self, episode_len=200):
+        super().__init__(episode_len)
 
 
 class FrameEnv(object):

@@ -14,7 +14,9 @@ per-episode host loop replaced by ONE batched rollout launch per epoch:
 
 ``antithetic=True`` evaluates +eps/-eps pairs (build extension; batch_size then counts directions).
 Environments are GPU-resident (envs/): the trap env exactly, MuJoCo / CartPole ids map to the
-build's synthetic fixed-length envs of the same shapes (no simulator exists on this platform).
+build's synthetic fixed-length envs of the same shapes (no simulator exists on this platform);
+``physics=True`` instead runs CartPole-v1 / -v0 and Pendulum ids on the kernel's own classic-control dynamics
+(envs.CartPoleEnv / PendulumEnv: gym's formulas, per-lane random resets, CartPole's early termination).
 ``procgen`` ids (the reference's ImpalaPolicy route, run_sequential.py:68-71) and Atari ``NoFrameskip``
 ids (BASELINE configs 4/5: the Impala conv stack on Atari-shaped frames) run ImpalaPolicy on the
 synthetic frame env (``envs_per_lane`` envs per perturbation, ``fp16`` rollouts for config 5), with the
@@ -29,7 +31,7 @@ import torch
 
 from dsgd import DSGD
 from fdr import engine
-from envs import FrameEnv, StackedFrameEnv, SyntheticEnv, TrapEnv
+from envs import CartPoleEnv, FrameEnv, PendulumEnv, StackedFrameEnv, SyntheticEnv, TrapEnv
 from learner import FDBatch, FDState, FiniteDifferences
 from policies import AtariPolicy, DiscretePolicy, ImpalaPolicy, MujocoPolicy
 from strategy import StrategyHandler
@@ -46,8 +48,24 @@ def frame_env_id(env_id):
     return "procgen" in env_id or "NoFrameskip" in env_id
 
 
+PHYSICS_IDS = "CartPole-v1, CartPole-v0, Pendulum*"
+
+
+def make_physics_env(env_id, episode_len=None):
+    """The classic-control envs the rollout kernel steps for real (envs.CartPoleEnv / PendulumEnv)."""
+    if env_id == "CartPole-v1":
+        return CartPoleEnv(500 if episode_len is None else episode_len)
+    if env_id == "CartPole-v0":
+        return CartPoleEnv(200 if episode_len is None else episode_len)
+    if env_id.startswith("Pendulum"):
+        return PendulumEnv(200 if episode_len is None else episode_len)
+    raise ValueError("physics=True supports the env ids %s (got %r)" % (PHYSICS_IDS, env_id))
+
+
 def make_env(env_id, device=None, episode_len=None, env_seed=0, n_act=None, envs_per_lane=1, fp16=False,
-             policy=None):
+             policy=None, physics=False):
+    if physics:
+        return make_physics_env(env_id, episode_len)
     if env_id.startswith("SimpleTrapEnv"):
         return TrapEnv(device=device)
     if frame_env_id(env_id):
@@ -79,7 +97,7 @@ class SequentialRunner(object):
                  omega_min_value=0, omega_max_value=1, omega_steps_to_min=25, omega_steps_to_max=75,
                  log_to_wandb=False, wandb_project="fd-starter", wandb_group=None, wandb_run_name=None,
                  noise_table_size=25_000_000, antithetic=False, episode_len=None, device=None, verbose=True,
-                 envs_per_lane=1, fp16=False, policy=None, noise_source="table"):
+                 envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False):
         if log_to_wandb:
             raise NotImplementedError("wandb logging is not part of the MI355X engine (no network)")
         self.verbose = verbose
@@ -94,7 +112,8 @@ class SequentialRunner(object):
         torch.manual_seed(random_seed)
         np.random.seed(random_seed)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.env = make_env(env_id, self.device, episode_len, envs_per_lane=envs_per_lane, fp16=fp16, policy=policy)
+        self.env = make_env(env_id, self.device, episode_len, envs_per_lane=envs_per_lane, fp16=fp16, policy=policy,
+                            physics=physics)
         self.frames = isinstance(self.env, FrameEnv)
         if isinstance(self.env, StackedFrameEnv):      # utils/init_helper.py:13-18
             self.policy = AtariPolicy(self.env.obs_shape, self.env.act_dim, seed=random_seed, device=self.device)

@@ -42,6 +42,16 @@ typedef void* fdr_stream; /* hipStream_t */
 /* Environments run inside the rollout kernel. */
 #define FDR_ENV_SYNTH 0 /* contractive linear-tanh system (DESIGN.md "Synthetic envs") */
 #define FDR_ENV_TRAP 1  /* custom_envs/simple_trap_env (integer-exact) */
+/* Classic-control physics (added within fdr 0.5: two constants, no new export, fdr_env_desc unchanged).  gym's
+   published classic_control formulas in f32; every lane resets to its own state, drawn from the counter
+   stream by its global lane id (lane_offset + lane), so a lane's episode does not depend on the launch or shard that
+   runs it.  Descriptor: M, K, s0 and walkable NULL, done_threshold 0, episode_len (the time limit) in 1 .. 10000,
+   else FDR_ERR_INVALID; a policy other than the one named here is FDR_ERR_UNSUPPORTED.  Served by fdr_rollout,
+   fdr_rollout_states and fdr_rollout_ex with every extra, always on the one-lane-per-wave kernel. */
+#define FDR_ENV_CARTPOLE 2 /* CartPole-v1: obs 4 / 2 actions, FDR_POLICY_DISCRETE; ends when the pole or cart leaves
+                              its bounds (reward 1 per step taken) or at episode_len */
+#define FDR_ENV_PENDULUM 3 /* Pendulum-v1: obs 3 (cos, sin, thetadot) / 1 action dim, FDR_POLICY_MUJOCO; the action is
+                              clamped to [-2, 2]; always runs episode_len steps */
 
 typedef struct fdr_policy_desc {
   int32_t kind;     /* FDR_POLICY_* */

@@ -107,6 +107,15 @@ int launch_policy_forward(const PolicyKey& k, const LanesArgs& lanes, int n_lane
                           const float* bn_mean, const float* bn_var, const float* x, float* out0,
                           float* out1, hipStream_t stream);
 int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream);
+// The rollout kernel families launch_rollout chooses from, one translation unit and one launcher each
+// (fdr_rollout_lane / _wide / _env / _pair.hip); each matches the policy shape and the feature set itself.
+// synthetic env, one lane per wave: the 128-VGPR kernel / the 256-VGPR one
+int launch_rollout_lane(const PolicyKey& k, const RolloutArgs& args, hipStream_t stream);
+int launch_rollout_wide(const PolicyKey& k, const RolloutArgs& args, hipStream_t stream);
+// trap gridworld, CartPole, Pendulum
+int launch_rollout_env(const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream);
+// two lanes per wave; round_lanes: lanes of one resident round (more go out as consecutive launches)
+int launch_rollout_pair(const PolicyKey& k, const RolloutArgs& args, int round_lanes, hipStream_t stream);
 // fdr_diag_theta_prime: what MlpLane::load / MlpPair::load read through a RecordSrc (out / reads / counted [n_lanes, P])
 int launch_theta_prime(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, int loader, const float* bn_mean,
                        const float* bn_var, float* out, int32_t* reads, int32_t* counted, double* n2,

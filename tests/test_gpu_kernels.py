@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 IMPL_NAMES = {0: "pair", 1: "single", 2: "auto", 3: "wide"}   # FDR_ROLLOUT_*
 SHAPES = {"trap": ("discrete", 2, 9), "cartpole": ("discrete", 4, 2), "cheetah": ("mujoco", 17, 6)}
 # the other compiled rollout shapes (no golden vectors: oracle parity only)
-ROLL_SHAPES = dict(SHAPES, lunar=("discrete", 8, 4), hopper=("mujoco", 11, 3))
+ROLL_SHAPES = dict(SHAPES, lunar=("discrete", 8, 4), hopper=("mujoco", 11, 3), swimmer=("mujoco", 8, 2))
 DEV = "cuda"
 
 
@@ -159,7 +159,10 @@ def test_rollout_vs_oracle(eng, name, det):
                                           ("cartpole", 13, False, 120), ("cartpole", 9, True, 120),
                                           ("cheetah", 64, False, 120), ("cheetah", 10, False, 123),
                                           ("cheetah", 6, False, 3), ("cartpole", 6, False, 37),
-                                          ("lunar", 13, False, 90), ("lunar", 8, True, 40), ("hopper", 11, False, 70)])
+                                          ("lunar", 13, False, 90), ("lunar", 8, True, 40), ("hopper", 11, False, 70),
+                                          # (mujoco, 8, 2): an idle half; 2 action dims make the pair kernel's draw
+                                          # batch 16 steps, so T = 19 is one full batch plus a remainder
+                                          ("swimmer", 7, False, 19)])
 def test_rollout_pair_and_single_kernels_agree(eng, name, L, det, T):
     """rollout_pair_kernel (two lanes per wave), rollout_kernel (one lane per wave) and its register-rich
     WIDE variant against the oracle and each other, incl. odd lane counts (a wave whose second half is

@@ -1,7 +1,7 @@
 """Dump the innermost loop (smallest backward-branch region containing v_pk_fma_f32 / MFMA) of a kernel
 in a hipcc -S listing, with its instruction mix.
 
-    python tools/loop_dump.py /tmp/fdr_rollout.s rollout_pair_kernelILi17ELi6ELb0ELi0E [out.s]
+    python tools/loop_dump.py /tmp/fdr_rollout_pair.s rollout_pair_kernelILi17ELi6ELb0ELi0E [out.s]
 """
 import re
 import sys

@@ -1,6 +1,6 @@
 """Instruction mix of the innermost hot loop of a kernel in a hipcc -S listing.
 
-    python tools/loop_stats.py /tmp/fdr_rollout.s rollout_kernelILi17ELi6ELb0ELi0
+    python tools/loop_stats.py /tmp/fdr_rollout_lane.s rollout_kernelILi17ELi6ELb0ELi0
 """
 import re
 import sys

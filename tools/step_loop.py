@@ -1,6 +1,6 @@
 """Instruction mix of the innermost loop of a kernel that contains a marker instruction (hipcc -S listing).
 
-    python tools/step_loop.py /tmp/fdr_rollout.s rollout_pair_kernelILi17ELi6ELb0ELi0 row_half_mirror [8] [--dump]
+    python tools/step_loop.py /tmp/fdr_rollout_pair.s rollout_pair_kernelILi17ELi6ELb0ELi0 row_half_mirror [8] [--dump]
 
 (the optional count = marker lines per step, to report the unroll factor)
 

@@ -1,6 +1,6 @@
 // fdr_atari.hip -- AtariPolicy (policies/atari.py:7-51) rollouts on gfx950.
 //
-// Same pack / prep / finish machinery as the ImpalaPolicy path (fdr_impala.hip): theta'_l gathered
+// Same pack / prep / finish machinery as the ImpalaPolicy path (fdr_pack.h, fdr_pack.hip): theta'_l gathered
 // once per rollout into a per-lane pack (conv weights as v_mfma_f32_16x16x4_f32 B-fragments with
 // 8x8 / 4x4 taps, fc W^T), then per step:
 //   atari_conv_kernel  one 512-thread workgroup per (lane, env): synthetic 4x84x84 stacked frame ->
@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <cfloat>
 
-#include "fdr_impala.h"
+#include "fdr_pack.h"
 
 namespace fdr {
 namespace atari {
@@ -271,13 +271,12 @@ struct Plan {
 };
 static Plan plan(const Layout& L, int n_lanes, int envs) {
   Plan p{};
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { const int64_t at = off; off += round_up(std::max<int64_t>(bytes, 0), 256); return at; };
+  impala::Carver ws;
   p.nblk = impala::prep_blocks(L);
-  p.pack = take((int64_t)n_lanes * L.pack * 4);
-  p.feat = take((int64_t)n_lanes * envs * kFeat * 4);
-  p.n2 = take((int64_t)n_lanes * p.nblk * 8);
-  p.total = off;
+  p.pack = ws.take((int64_t)n_lanes * L.pack * 4);
+  p.feat = ws.take((int64_t)n_lanes * envs * kFeat * 4);
+  p.n2 = ws.take((int64_t)n_lanes * p.nblk * 8);
+  p.total = ws.used;
   return p;
 }
 

@@ -12,7 +12,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "fdr_impala.h"
+#include "fdr_impala_kernels.h"
 
 namespace fdr {
 namespace impala {

@@ -302,25 +302,20 @@ struct VbnPlan {
 
 VbnPlan vbn_plan(int n) {
   VbnPlan p{};
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t at = off;
-    off += (bytes + 255) / 256 * 256;
-    return at;
-  };
-  p.A = take((int64_t)n * kCh[0] * 64 * 64 * 4);
-  p.X = take((int64_t)n * kCh[0] * 32 * 32 * 4);
-  p.Y = take((int64_t)n * kCh[0] * 32 * 32 * 4);
-  p.CI = take((int64_t)n * kCoreIn * 4);
-  p.GX = take((int64_t)n * kGates * 4);
-  p.HS = take((int64_t)n * kHid * 4);
-  p.WTfc = take((int64_t)kFeat * kHid * 4);
-  p.WTih = take((int64_t)kCoreIn * kGates * 4);
-  p.WThh = take((int64_t)kHid * kGates * 4);
-  p.part = take((int64_t)kFeat * kStatBlocks * 2 * 8);
-  p.scale = take((int64_t)kFeat * 4);
-  p.shift = take((int64_t)kFeat * 4);
-  p.total = off;
+  impala::Carver ws;
+  p.A = ws.take((int64_t)n * kCh[0] * 64 * 64 * 4);
+  p.X = ws.take((int64_t)n * kCh[0] * 32 * 32 * 4);
+  p.Y = ws.take((int64_t)n * kCh[0] * 32 * 32 * 4);
+  p.CI = ws.take((int64_t)n * kCoreIn * 4);
+  p.GX = ws.take((int64_t)n * kGates * 4);
+  p.HS = ws.take((int64_t)n * kHid * 4);
+  p.WTfc = ws.take((int64_t)kFeat * kHid * 4);
+  p.WTih = ws.take((int64_t)kCoreIn * kGates * 4);
+  p.WThh = ws.take((int64_t)kHid * kGates * 4);
+  p.part = ws.take((int64_t)kFeat * kStatBlocks * 2 * 8);
+  p.scale = ws.take((int64_t)kFeat * 4);
+  p.shift = ws.take((int64_t)kFeat * 4);
+  p.total = ws.used;
   return p;
 }
 
@@ -494,20 +489,15 @@ struct AVbnPlan {
 
 AVbnPlan avbn_plan(int n) {
   AVbnPlan p{};
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t at = off;
-    off += (bytes + 255) / 256 * 256;
-    return at;
-  };
-  p.X1 = take((int64_t)n * kA1 * kO1 * kO1 * 4);
-  p.X2 = take((int64_t)n * kAFeat * 4);
-  p.F = take((int64_t)n * kAFc * 4);
-  p.WT = take((int64_t)kAFeat * kAFc * 4);
-  p.part = take((int64_t)kAFc * impala::kStatBlocks * 2 * 8);
-  p.scale = take((int64_t)kAFc * 4);
-  p.shift = take((int64_t)kAFc * 4);
-  p.total = off;
+  impala::Carver ws;
+  p.X1 = ws.take((int64_t)n * kA1 * kO1 * kO1 * 4);
+  p.X2 = ws.take((int64_t)n * kAFeat * 4);
+  p.F = ws.take((int64_t)n * kAFc * 4);
+  p.WT = ws.take((int64_t)kAFeat * kAFc * 4);
+  p.part = ws.take((int64_t)kAFc * impala::kStatBlocks * 2 * 8);
+  p.scale = ws.take((int64_t)kAFc * 4);
+  p.shift = ws.take((int64_t)kAFc * 4);
+  p.total = ws.used;
   return p;
 }
 

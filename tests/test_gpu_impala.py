@@ -603,6 +603,111 @@ def test_fp16_conv_stack_forward_and_strategies_vs_oracle(engine, table):
     np.testing.assert_allclose(st.cpu().numpy(), ref, atol=F16_RTOL)
 
 
+# ---- the step plan: the rows no test above reaches, at the smallest shape that reaches them ----
+_FIELDS = ("actions", "probs", "reward", "entropy", "norm2")
+
+
+def _pair_batch(engine, table, theta, n_pairs):
+    idx = np.repeat(np.array([77, 2_000_000, 3_000_000], np.int64)[:n_pairs], 2)
+    sign = np.tile(np.array([1, -1], np.int8), n_pairs)
+    lanes = engine.lanes_desc(torch.tensor(theta, device="cuda"), 0, torch.tensor(table, device="cuda"),
+                              torch.tensor(idx, device="cuda"), torch.tensor(sign, device="cuda"), 0.02)
+    return lanes, idx, sign
+
+
+def _episode(engine, spec, lanes, L, seed=11):
+    o = engine.impala_rollout(spec, lanes, L, seed, record=True)
+    torch.cuda.synchronize()
+    return {f: getattr(o, f).cpu().numpy().copy() for f in _FIELDS}
+
+
+def _fp16_pair_episode_vs_f32_oracle(out, theta, table, idx, sign, A, E, T, seed=11, entropy=True):
+    """The bounds of test_fp16_pair_form_episodes_vs_f32_oracle on one recorded batch."""
+    from oracle import rng as crng
+    L = len(idx)
+    acts = out["actions"].reshape(L, E, T)
+    nb = oi.num_bn()
+    ref = oi.follow_lanes(theta, table, idx, sign, 0.02, A, E, T, 5, np.zeros(nb, np.float32), np.ones(nb, np.float32),
+                          acts)
+    jig = np.stack([crng.jiggle(seed, np.uint64(l) * np.uint64(E) + np.arange(E, dtype=np.uint64)) for l in range(L)])
+    ent = out["entropy"].reshape(L, E)
+    if not entropy:  # no replay ran: the entropy is reported as 0 and there is nothing to bound
+        assert np.all(ent == 0.0)
+        ent = ref["ent"]
+    _, _, amb = _check_vs_followed_oracle(out["probs"].reshape(L, E, T, A), acts, out["reward"].reshape(L, E) - jig, ent,
+                                          ref, seed, range(L), E, F16_RTOL)
+    assert amb <= 0.01 * L * E * T
+    np.testing.assert_array_equal(out["norm2"][0::2], out["norm2"][1::2])
+
+
+@pytest.mark.parametrize("fp16,pairs", [(False, False), (False, True), (True, False), (True, True)])
+def test_replay_chunk_tail_with_and_without_gemm(engine, table, fp16, pairs):
+    """T = 65: the entropy replay crosses the 64-step chunk boundary with a one-step tail; 4 lanes x 1 env (one
+    core_kernel_hpm2 workgroup).  With the input-projection GEMM on and off (fdr_ctx_set_replay_gemm) the f32 forms and
+    the fp16 per-lane form run the same fma chains: whole recorded episodes bitwise identical, and the f32 pair form
+    (core_kernel_p, then core_kernel_pr with the GEMM / core_kernel<kReplay> without) bitwise the per-lane form.  The
+    fp16 pair form replays on replay_chunk_hpm2 with the GEMM and per lane (core_kernel_h<kReplay>) without: each within
+    the pair form's bounds of the f32 oracle."""
+    A, E, T, n_pairs = 5, 1, 65, 2
+    theta = _theta(A)
+    lanes, idx, sign = _pair_batch(engine, table, theta, n_pairs)
+    L = len(idx)
+    spec = engine.ImpalaSpec(A, E, T, entropy=True, env_seed=5, fp16=fp16, pairs=pairs)
+    runs = {}
+    try:
+        for on in (1, 0):
+            engine.context().set_replay_gemm(on)
+            runs[on] = _episode(engine, spec, lanes, L)
+    finally:
+        engine.context().set_replay_gemm(True)
+    if fp16 and pairs:
+        for on in (1, 0):
+            _fp16_pair_episode_vs_f32_oracle(runs[on], theta, table, idx, sign, A, E, T)
+        return
+    assert np.all(np.isfinite(runs[1]["entropy"])) and np.all(runs[1]["entropy"] != 0)
+    for f in _FIELDS:
+        np.testing.assert_array_equal(runs[1][f], runs[0][f], err_msg=f)
+    if pairs:
+        lane = _episode(engine, engine.ImpalaSpec(A, E, T, entropy=True, env_seed=5), lanes, L)
+        for f in _FIELDS:
+            np.testing.assert_array_equal(runs[1][f], lane[f], err_msg=f)
+
+
+@pytest.mark.parametrize("fp16", [False, True])
+def test_pair_form_without_entropy(engine, table, fp16):
+    """The pair forms of the rollout step alone (entropy off: no projection, no replay), T = 3, 4 lanes x 1 env: f32
+    bitwise the per-lane form, fp16 within the pair form's bounds of the f32 oracle."""
+    A, E, T = 5, 1, 3
+    theta = _theta(A)
+    lanes, idx, sign = _pair_batch(engine, table, theta, 2)
+    out = _episode(engine, engine.ImpalaSpec(A, E, T, entropy=False, env_seed=5, fp16=fp16, pairs=True), lanes, 4)
+    if fp16:
+        _fp16_pair_episode_vs_f32_oracle(out, theta, table, idx, sign, A, E, T, entropy=False)
+        return
+    lane = _episode(engine, engine.ImpalaSpec(A, E, T, entropy=False, env_seed=5), lanes, 4)
+    for f in _FIELDS:
+        np.testing.assert_array_equal(out[f], lane[f], err_msg=f)
+    assert np.all(out["entropy"] == 0.0)
+
+
+@pytest.mark.parametrize("fp16", [False, True])
+def test_eight_envs_run_per_lane_under_pairs(engine, table, fp16):
+    """E = 8 has no pair form: with fdr_impala_desc.pairs set the call runs the per-lane kernels, bitwise a pairs = False
+    launch (T = 3 with the entropy replay, 4 lanes); the f32 episodes are the oracle's."""
+    A, E, T = 5, 8, 3
+    theta = _theta(A)
+    lanes, idx, sign = _pair_batch(engine, table, theta, 2)
+    o = [_episode(engine, engine.ImpalaSpec(A, E, T, entropy=True, env_seed=5, fp16=fp16, pairs=pr), lanes, 4)
+         for pr in (False, True)]
+    assert np.all(np.isfinite(o[1]["entropy"])) and np.all(o[1]["entropy"] > 0)
+    for f in _FIELDS:
+        np.testing.assert_array_equal(o[0][f], o[1][f], err_msg=f)
+    if not fp16:
+        out, ref = _run(engine, table, A, E, T, idx, sign, [0] * 4)
+        _compare(out, ref, 4, E, T, A)
+        np.testing.assert_array_equal(out.probs.cpu().numpy(), o[1]["probs"])
+
+
 @pytest.mark.parametrize("fp16,pairs", [(False, False), (False, True), (True, False), (True, True)])
 def test_full_size_rollout_properties(engine, fp16, pairs):
     """BASELINE configs 4/5 at full size (1024 lanes x 4 envs x T = 1000, A = 6 / 4): bitwise reproducible (a

@@ -69,6 +69,16 @@ def test_a_shifted_load_address_and_another_encoding_are_no_difference():
     assert idf.diff(old, new) == []
 
 
+def test_padding_after_the_last_instruction_is_no_difference():
+    # the function that ends a code object carries that object's end padding; one in the middle only its alignment
+    old = _build({"k": _BODY + ["s_nop 0"] * 3, "k2": _BODY})
+    new = _build({"k2": _BODY, "k": _BODY + ["s_nop 0"] * 260})
+    assert idf.diff(old, new) == []
+    # an s_nop inside the function still counts
+    body = _BODY[:2] + ["s_nop 0"] + _BODY[2:]
+    assert len(idf.diff(_build({"k": _BODY}), _build({"k": body}))) == 1
+
+
 def test_one_changed_operand_is_a_difference():
     body = list(_BODY)
     body[1] = "v_add_f32_e32 v4, v1, v3"

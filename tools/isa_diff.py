@@ -3,7 +3,9 @@
 For a refactor that must not change any kernel: every function symbol of OLD.so and NEW.so is disassembled
 (tools/isa_hazards.code_objects) and its instruction stream compared -- mnemonic and the full operand text, a
 branch by its symbol-relative target.  Load addresses and encodings are ignored, so a function that merely moved
-inside its code object, or into another one, compares equal.  The kernel metadata is compared too: VGPR, AGPR and
+inside its code object, or into another one, compares equal -- including to the end of one: the s_nop padding after a
+function's last instruction (alignment of the next function; ~256 of them after the last function of a code object)
+is no part of it and is dropped.  The kernel metadata is compared too: VGPR, AGPR and
 SGPR counts, LDS bytes, scratch bytes, max flat workgroup size.  Symbols on one side only are listed.
 
 Usage: python tools/isa_diff.py OLD.so NEW.so      (exit 1 on any difference)
@@ -25,7 +27,8 @@ _META = re.compile(r"^(\s*)(- )?\.(\w+):\s*(.*?)\s*$")
 
 def streams(asm_text):
     """{function: [(mnemonic, operands)]} of an llvm-objdump -d listing; a branch's operand is its target as
-    'symbol+0xoffset' (the annotation objdump prints), every other instruction's its operand text as printed."""
+    'symbol+0xoffset' (the annotation objdump prints), every other instruction's its operand text as printed.  Trailing
+    's_nop 0' padding is dropped."""
     funcs, cur = {}, None
     for line in asm_text.splitlines():
         m = _FUNC.match(line)
@@ -39,6 +42,9 @@ def streams(asm_text):
         if tfun and (mn.startswith("s_cbranch") or mn == "s_branch"):
             rest = "%s+0x%s" % (tfun, toff)
         cur.append((mn, rest))
+    for ins in funcs.values():
+        while ins and ins[-1] == ("s_nop", "0"):
+            ins.pop()
     return funcs
 
 

@@ -8,28 +8,10 @@
 #include <string>
 
 #include "../../include/fdr_diag.h"
+#include "fdr_atari.h"
 #include "fdr_impala.h"
 #include "fdr_internal.h"
-
-namespace fdr {
-namespace atari {
-int64_t num_params(int n_act);
-int64_t workspace_bytes(int n_act, int n_lanes, int envs);
-int64_t forward_workspace_bytes(int n_act, int n);
-int launch_rollout(int n_act, int envs, int T, uint64_t env_seed, const LanesArgs& lanes, int n_lanes, uint64_t seed,
-                   int jiggle, const float* bn_mean, const float* bn_var, double* ret, double* ent, int32_t* steps,
-                   double* norm2, int32_t* actions, float* probs, void* ws, int64_t ws_bytes, hipStream_t stream);
-int launch_forward(int n_act, const float* theta, int n, const float* frames, const float* bn_mean,
-                   const float* bn_var, float* probs, float* feat, void* ws, int64_t ws_bytes, hipStream_t stream);
-int launch_env_frames(uint64_t env_seed, uint64_t env_id, int t0, int n, float* frames, hipStream_t stream);
-int64_t strategies_workspace_bytes(int n_act, int n_lanes, int Z);
-int launch_strategies(int n_act, const LanesArgs& lanes, int n_lanes, int Z, const float* frames, const float* bn_mean,
-                      const float* bn_var, float* probs, void* ws, int64_t ws_bytes, hipStream_t stream);
-int64_t vbn_workspace_bytes(int n);  // (fdr_impala_vbn.hip)
-int launch_vbn(const float* theta, int n, const float* frames, float momentum, float* bn_mean, float* bn_var, void* ws,
-               int64_t ws_bytes, hipStream_t stream);
-}  // namespace atari
-}  // namespace fdr
+#include "fdr_learner.h"
 
 namespace fdr {
 
@@ -49,29 +31,26 @@ int check_launch(const char* what) {
   return FDR_OK;
 }
 
-int launch_perturb(const float* theta, int64_t P, const float* table, int64_t table_size,
-                   const int64_t* idx, const int8_t* sign, int n, float sigma, float* out,
-                   hipStream_t stream);
-int launch_fd_weights(const double* r_all, int n_all, double pr, int lo, int n_local,
-                      const int8_t* sign, const double* n2, int lpd, float sigma, double* coef,
-                      hipStream_t stream);
-int64_t grad_workspace_bytes(int n_dirs, int64_t P);
-int launch_fd_grad(const float* table, int64_t table_size, const int64_t* idx, const double* coef,
-                   int n_dirs, int64_t P, double* g, void* ws, int64_t ws_bytes, hipStream_t stream);
-int64_t dsgd_workspace_bytes(int64_t P);
-int launch_strategy_dist(const float* S, int n, const float* B, int H, int Z, int D, int kind, double* dists,
-                         double* min_d, int32_t* arg, hipStream_t stream);
-int launch_dsgd(float* theta, const double* g, int64_t P, double lr, double lr_scale, double* out,
-                void* ws, int64_t ws_bytes, hipStream_t stream);
-int launch_dsgd_ex(float* theta, const double* src, int mom, int64_t P, double lr, double lr_scale, double* g_out,
-                   double* out, void* ws, int64_t ws_bytes, hipStream_t stream);
-int64_t fused_workspace_bytes(int n_dirs, int n_local, int64_t P, int mode);
-int64_t fused_counter_bytes(int n_dirs, int64_t P);
-int launch_fd_grad_fused(const float* table, int64_t table_size, const int64_t* idx, int n_dirs, int64_t P,
-                         const double* r_all, int n_all, double pr, int lo, const int8_t* sign, const double* n2,
-                         int lpd, float sigma, int mode, double* out, float* theta, double lr, double lr_scale,
-                         float* hist, double* dsgd_out, void* ws, int64_t ws_bytes, hipStream_t stream);
-int launch_rank_weights(const double* r_all, int n_all, int lo, int n_local, double* w, hipStream_t stream);
+Context& default_context() {
+  static Context* d = [] {
+    Context* c = new Context();
+    const char* e = getenv("FDR_ROLLOUT");
+    c->rollout_impl = !e ? FDR_ROLLOUT_AUTO
+                         : strcmp(e, "single") == 0 ? FDR_ROLLOUT_SINGLE
+                         : strcmp(e, "wide") == 0   ? FDR_ROLLOUT_WIDE
+                                                    : strcmp(e, "pair") == 0 ? FDR_ROLLOUT_PAIR : FDR_ROLLOUT_AUTO;
+    return c;
+  }();
+  return *d;
+}
+
+int context_cus(const Context& c) {
+  if (c.cus > 0) return c.cus;
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 256;
+  return cus;
+}
 
 static int policy_key(const fdr_policy_desc* p, PolicyKey* k) {
   if (!p) return set_error(FDR_ERR_INVALID, "policy desc is NULL");
@@ -114,29 +93,6 @@ struct fdr_ctx {
   fdr::Context c;
 };
 
-namespace fdr {
-Context& default_context() {
-  static Context* d = [] {
-    Context* c = new Context();
-    const char* e = getenv("FDR_ROLLOUT");
-    c->rollout_impl = !e ? FDR_ROLLOUT_AUTO
-                         : strcmp(e, "single") == 0 ? FDR_ROLLOUT_SINGLE
-                         : strcmp(e, "wide") == 0   ? FDR_ROLLOUT_WIDE
-                                                    : strcmp(e, "pair") == 0 ? FDR_ROLLOUT_PAIR : FDR_ROLLOUT_AUTO;
-    return c;
-  }();
-  return *d;
-}
-
-int context_cus(const Context& c) {
-  if (c.cus > 0) return c.cus;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 256;
-  return cus;
-}
-}  // namespace fdr
-
 // The context of a call: ctx, or the default one; a ctx is bound to its device (the caller's current device
 // must be that device -- its stream belongs to it).
 static int resolve(fdr_ctx* ctx, Context** out) {
@@ -154,6 +110,9 @@ static int resolve(fdr_ctx* ctx, Context** out) {
   *out = &ctx->c;
   return FDR_OK;
 }
+
+// The setters' context: no device check (unlike FDR_CTX) -- they touch host state only.
+static Context& ctx_or_default(fdr_ctx* ctx) { return ctx ? ctx->c : default_context(); }
 
 #define FDR_CTX(ctx, C)          \
   Context* C = nullptr;          \
@@ -175,18 +134,18 @@ static int set_impl(Context& c, int32_t impl) {
   return FDR_OK;
 }
 int fdr_rollout_set_impl(int32_t impl) { return set_impl(default_context(), impl); }
-int fdr_ctx_set_rollout_impl(fdr_ctx* ctx, int32_t impl) { return set_impl(ctx ? ctx->c : default_context(), impl); }
+int fdr_ctx_set_rollout_impl(fdr_ctx* ctx, int32_t impl) { return set_impl(ctx_or_default(ctx), impl); }
 int fdr_ctx_set_replay_gemm(fdr_ctx* ctx, int32_t on) {
-  (ctx ? ctx->c : default_context()).replay_gemm = on != 0;
+  ctx_or_default(ctx).replay_gemm = on != 0;
   return FDR_OK;
 }
-int fdr_ctx_impala_profile(fdr_ctx* ctx, int32_t enable) { return impala::set_profile(ctx ? ctx->c : default_context(), enable); }
+int fdr_ctx_impala_profile(fdr_ctx* ctx, int32_t enable) { return impala::set_profile(ctx_or_default(ctx), enable); }
 int fdr_ctx_impala_profile_read(fdr_ctx* ctx, double* ms) {
   if (!ms) return set_error(FDR_ERR_INVALID, "NULL pointer");
-  return impala::read_profile(ctx ? ctx->c : default_context(), ms);
+  return impala::read_profile(ctx_or_default(ctx), ms);
 }
 int fdr_ctx_impala_debug_clock(fdr_ctx* ctx, uint64_t* buf) {
-  (ctx ? ctx->c : default_context()).debug_clock = buf;
+  ctx_or_default(ctx).debug_clock = buf;
   return FDR_OK;
 }
 
@@ -409,7 +368,9 @@ int fdr_fd_grad(fdr_ctx* ctx, const float* table, int64_t table_size, const int6
                         workspace_bytes, (hipStream_t)stream);
 }
 
-int64_t fdr_dsgd_workspace_bytes(int64_t n_params) { return dsgd_workspace_bytes(n_params); }
+int64_t fdr_dsgd_workspace_bytes(int64_t n_params) {
+  return dsgd_workspace_bytes(n_params);
+}
 
 int fdr_dsgd_step(fdr_ctx* ctx, float* theta, const double* g, int64_t n_params, double lr,
                   double lr_scale, double* out, void* workspace, int64_t workspace_bytes,
@@ -460,9 +421,28 @@ static int fd_grad_fused_impl(const float* table, int64_t table_size, const int6
   const int n_local = n_dirs * lanes_per_dir;
   if (!idx_local || !rewards_all || !sign_local || !norm2_local) return set_error(FDR_ERR_INVALID, "NULL pointer");
   if (n_all <= 0 || lane_lo < 0 || lane_lo + n_local > n_all) return set_error(FDR_ERR_INVALID, "bad lane range");
-  return launch_fd_grad_fused(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward,
-                              lane_lo, sign_local, norm2_local, lanes_per_dir, sigma, mode, out, theta, lr, lr_scale,
-                              hist, dsgd_out, workspace, workspace_bytes, (hipStream_t)stream);
+  FusedCall c{};
+  c.fd.table = table;
+  c.fd.max_idx = table_size - n_params;
+  c.fd.idx = idx_local;
+  c.fd.n_dirs = n_dirs;
+  c.fd.P = n_params;
+  c.fd.r_all = rewards_all;
+  c.fd.n_all = n_all;
+  c.fd.pr = policy_reward;
+  c.fd.lo = lane_lo;
+  c.fd.sign = sign_local;
+  c.fd.n2 = norm2_local;
+  c.fd.lpd = lanes_per_dir;
+  c.fd.sigma = sigma;
+  c.fd.out = out;
+  c.mode = mode;
+  c.theta = theta;
+  c.lr = lr;
+  c.lr_scale = lr_scale;
+  c.hist = hist;
+  c.dsgd_out = dsgd_out;
+  return launch_fd_grad_fused(c, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int fdr_fd_grad_fused(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
@@ -598,7 +578,9 @@ int fdr_impala_forward(fdr_ctx* ctx, const fdr_impala_desc* d, const float* thet
   return impala::launch_forward(f, ws, ws_bytes, (hipStream_t)stream);
 }
 
-int64_t fdr_impala_bn_refresh_workspace_bytes(int32_t n) { return n < 0 ? -1 : impala::vbn_workspace_bytes(n); }
+int64_t fdr_impala_bn_refresh_workspace_bytes(int32_t n) {
+  return n < 0 ? -1 : impala::vbn_workspace_bytes(n);
+}
 
 int fdr_impala_bn_refresh(fdr_ctx* ctx, const fdr_impala_desc* d, const float* theta, int32_t n, const float* frames,
                           const float* reward, int32_t first_done, float* h, float* c, float momentum, float* bn_mean,
@@ -710,7 +692,9 @@ int fdr_fd_grad_lambda(fdr_ctx* ctx, const float* table, int64_t table_size, con
   return launch_lambda_grad(R, coef, n, g, ws, ws_bytes, (hipStream_t)stream);
 }
 
-int64_t fdr_bn_refresh_workspace_bytes(int32_t n) { return n < 0 ? -1 : bn_refresh_workspace_bytes(n); }
+int64_t fdr_bn_refresh_workspace_bytes(int32_t n) {
+  return n < 0 ? -1 : bn_refresh_workspace_bytes(n);
+}
 
 int fdr_bn_refresh(fdr_ctx* ctx, const fdr_policy_desc* policy, const float* theta, const float* x, int32_t n,
                    float momentum, float* bn_mean, float* bn_var, void* ws, int64_t ws_bytes, fdr_stream stream) {
@@ -726,6 +710,15 @@ int fdr_bn_refresh(fdr_ctx* ctx, const fdr_policy_desc* policy, const float* the
 // ---- AtariPolicy ---------------------------------------------------------------------------------------
 int64_t fdr_atari_num_params(int32_t n_act) { return atari::num_params(n_act); }
 
+// The descriptor checks every Atari entry point starts with; *P = the parameter count of d->n_act
+static int atari_desc(const fdr_atari_desc* d, int64_t* P) {
+  if (!d) return set_error(FDR_ERR_INVALID, "atari desc is NULL");
+  *P = atari::num_params(d->n_act);
+  if (*P < 0) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
+  if (d->n_params != *P) return set_error(FDR_ERR_INVALID, "n_params does not match the AtariPolicy layout");
+  return FDR_OK;
+}
+
 int64_t fdr_atari_workspace_bytes(const fdr_atari_desc* d, int32_t n_lanes) {
   if (!d || n_lanes < 0) return -1;
   return atari::workspace_bytes(d->n_act, n_lanes, d->envs_per_lane);
@@ -735,19 +728,32 @@ int fdr_atari_rollout(fdr_ctx* ctx, const fdr_atari_desc* d, const fdr_lanes_des
                       uint64_t seed, int32_t jiggle, double* ret, double* ent, int32_t* steps, double* norm2,
                       int32_t* actions, float* probs, void* ws, int64_t ws_bytes, fdr_stream stream) {
   FDR_CTX(ctx, C);
-  if (!d) return set_error(FDR_ERR_INVALID, "atari desc is NULL");
-  const int64_t P = atari::num_params(d->n_act);
-  if (P < 0) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
-  if (d->n_params != P) return set_error(FDR_ERR_INVALID, "n_params does not match the AtariPolicy layout");
+  int64_t P;
+  int rc = atari_desc(d, &P);
+  if (rc) return rc;
   const int E = d->envs_per_lane;
   if (E != 1 && E != 2 && E != 4) return set_error(FDR_ERR_UNSUPPORTED, "envs_per_lane must be 1, 2 or 4");
   if (d->episode_len <= 0 || d->episode_len >= (1 << 20)) return set_error(FDR_ERR_INVALID, "episode_len out of range");
   if (!ret || !ent || !steps) return set_error(FDR_ERR_INVALID, "NULL output");
-  LanesArgs la;
-  int rc = lanes_args(lanes, n_lanes, P, &la);
+  atari::RolloutCall c{};
+  rc = lanes_args(lanes, n_lanes, P, &c.lanes);
   if (rc) return rc;
-  return atari::launch_rollout(d->n_act, E, d->episode_len, d->env_seed, la, n_lanes, seed, jiggle, d->bn_mean,
-                               d->bn_var, ret, ent, steps, norm2, actions, probs, ws, ws_bytes, (hipStream_t)stream);
+  c.n_act = d->n_act;
+  c.envs = E;
+  c.T = d->episode_len;
+  c.env_seed = d->env_seed;
+  c.n_lanes = n_lanes;
+  c.seed = seed;
+  c.jiggle = jiggle;
+  c.bn_mean = d->bn_mean;
+  c.bn_var = d->bn_var;
+  c.ret = ret;
+  c.ent = ent;
+  c.steps = steps;
+  c.norm2 = norm2;
+  c.actions = actions;
+  c.probs = probs;
+  return atari::launch_rollout(c, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int64_t fdr_atari_forward_workspace_bytes(int32_t n_act, int32_t n) {
@@ -764,27 +770,28 @@ int fdr_atari_env_frames(uint64_t env_seed, int64_t env_id, int32_t t0, int32_t 
 int fdr_atari_forward(fdr_ctx* ctx, const fdr_atari_desc* d, const float* theta, int32_t n, const float* frames,
                       float* probs, float* feat, void* ws, int64_t ws_bytes, fdr_stream stream) {
   FDR_CTX(ctx, C);
-  if (!d) return set_error(FDR_ERR_INVALID, "atari desc is NULL");
-  const int64_t P = atari::num_params(d->n_act);
-  if (P < 0) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
-  if (d->n_params != P) return set_error(FDR_ERR_INVALID, "n_params does not match the AtariPolicy layout");
+  int64_t P;
+  int rc = atari_desc(d, &P);
+  if (rc) return rc;
   if (!theta || !frames || !probs || n < 0) return set_error(FDR_ERR_INVALID, "NULL pointer / bad n");
-  return atari::launch_forward(d->n_act, theta, n, frames, d->bn_mean, d->bn_var, probs, feat, ws, ws_bytes,
-                               (hipStream_t)stream);
+  const atari::ForwardCall f{d->n_act, theta, n, frames, d->bn_mean, d->bn_var, probs, feat};
+  return atari::launch_forward(f, ws, ws_bytes, (hipStream_t)stream);
 }
 
-int64_t fdr_atari_bn_refresh_workspace_bytes(int32_t n) { return atari::vbn_workspace_bytes(n); }
+int64_t fdr_atari_bn_refresh_workspace_bytes(int32_t n) {
+  return atari::vbn_workspace_bytes(n);
+}
 
 int fdr_atari_bn_refresh(fdr_ctx* ctx, const fdr_atari_desc* d, const float* theta, int32_t n, const float* frames,
                          float momentum, float* bn_mean, float* bn_var, void* ws, int64_t ws_bytes, fdr_stream stream) {
   FDR_CTX(ctx, C);
-  if (!d) return set_error(FDR_ERR_INVALID, "atari desc is NULL");
-  const int64_t P = atari::num_params(d->n_act);
-  if (P < 0) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
-  if (d->n_params != P) return set_error(FDR_ERR_INVALID, "n_params does not match the AtariPolicy layout");
+  int64_t P;
+  int rc = atari_desc(d, &P);
+  if (rc) return rc;
   if (!theta || !frames || !bn_mean || !bn_var) return set_error(FDR_ERR_INVALID, "NULL pointer");
   if (n < 2) return set_error(FDR_ERR_INVALID, "train-mode BatchNorm1d needs n >= 2 samples");
-  return atari::launch_vbn(theta, n, frames, momentum, bn_mean, bn_var, ws, ws_bytes, (hipStream_t)stream);
+  const atari::VbnCall v{theta, n, frames, momentum, bn_mean, bn_var};
+  return atari::launch_vbn(v, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int64_t fdr_atari_strategies_workspace_bytes(const fdr_atari_desc* d, int32_t n_lanes, int32_t n_states) {
@@ -796,94 +803,19 @@ int fdr_atari_strategies(fdr_ctx* ctx, const fdr_atari_desc* d, const fdr_lanes_
                          int32_t n_states, const float* frames, float* probs, void* ws, int64_t ws_bytes,
                          fdr_stream stream) {
   FDR_CTX(ctx, C);
-  if (!d) return set_error(FDR_ERR_INVALID, "atari desc is NULL");
-  const int64_t P = atari::num_params(d->n_act);
-  if (P < 0) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
-  if (d->n_params != P) return set_error(FDR_ERR_INVALID, "n_params does not match the AtariPolicy layout");
-  if (n_states < 0 || (n_states > 0 && (!frames || !probs))) return set_error(FDR_ERR_INVALID, "NULL pointer / bad Z");
-  LanesArgs la;
-  int rc = lanes_args(lanes, n_lanes, P, &la);
+  int64_t P;
+  int rc = atari_desc(d, &P);
   if (rc) return rc;
-  return atari::launch_strategies(d->n_act, la, n_lanes, n_states, frames, d->bn_mean, d->bn_var, probs, ws, ws_bytes,
-                                  (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Host index draw (utils/noise_sources.py:44-47: one RandomState.randint(0, max_idx) per sample).  MT19937
-// (Matsumoto & Nishimura 1998, the generator behind numpy's legacy RandomState) advanced in place from the
-// state numpy reports (key[624], pos), and numpy's masked rejection for ranges that fit 32 bits: each draw takes
-// 32-bit words masked by the smallest all-ones mask >= max_idx - 1 until one is <= max_idx - 1.  numpy makes
-// one indirect generator call and one unpredictable branch per word (~11 ns per index on the build host); a block
-// of tempered words with a branch-free compaction takes ~2.5 ns, which keeps an 8-rank step's 16,384-index draw
-// (every rank consumes the whole stream) well under the rollout it overlaps.
-// ---------------------------------------------------------------------------------------------
-namespace {
-constexpr int kMtN = 624, kMtM = 397;
-
-void mt_refill(uint32_t* key) {
-  auto mix = [](uint32_t hi, uint32_t lo, uint32_t far) {
-    const uint32_t y = (hi & 0x80000000u) | (lo & 0x7fffffffu);
-    return far ^ (y >> 1) ^ ((0u - (y & 1u)) & 0x9908b0dfu);
-  };
-  int i = 0;
-  for (; i < kMtN - kMtM; ++i) key[i] = mix(key[i], key[i + 1], key[i + kMtM]);
-  for (; i < kMtN - 1; ++i) key[i] = mix(key[i], key[i + 1], key[i + kMtM - kMtN]);
-  key[kMtN - 1] = mix(key[kMtN - 1], key[0], key[kMtM - 1]);
-}
-
-inline uint32_t mt_temper(uint32_t y) {
-  y ^= y >> 11;
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  return y ^ (y >> 18);
-}
-}  // namespace
-
-extern "C" int fdr_noise_draw_indices(uint32_t* key, int32_t* pos, int64_t max_idx, int32_t n, int64_t* out) {
-  using namespace fdr;
-  if (!key || !pos || (n > 0 && !out) || n < 0) return set_error(FDR_ERR_INVALID, "NULL pointer / bad n");
-  if (max_idx < 1) return set_error(FDR_ERR_INVALID, "max_idx must be >= 1");
-  if (*pos < 0 || *pos > kMtN) return set_error(FDR_ERR_INVALID, "MT19937 pos out of range");
-  const uint64_t rng = (uint64_t)max_idx - 1;  // inclusive range of randint(0, max_idx)
-  if (rng > 0xFFFFFFFFull) return set_error(FDR_ERR_UNSUPPORTED, "index range wider than 32 bits");
-  if (rng == 0) {  // numpy returns the offset without drawing
-    for (int32_t i = 0; i < n; ++i) out[i] = 0;
-    return FDR_OK;
-  }
-  uint32_t mask = (uint32_t)rng;
-  mask |= mask >> 1;
-  mask |= mask >> 2;
-  mask |= mask >> 4;
-  mask |= mask >> 8;
-  mask |= mask >> 16;
-  // a refill block at a time: temper + mask the block's remaining words (vectorised), then a branch-free
-  // compaction keeps the accepted ones; the last block stops at the word that completes the n-th index, as
-  // numpy's loop does (no extra words consumed)
-  int p = *pos;
-  int32_t k = 0;
-  uint32_t buf[kMtN];
-  while (k < n) {
-    if (p == kMtN) {
-      mt_refill(key);
-      p = 0;
-    }
-    const int m = kMtN - p;
-    for (int i = 0; i < m; ++i) buf[i] = mt_temper(key[p + i]) & mask;
-    if (n - k >= m) {  // the whole block fits: k < n at every write
-      for (int i = 0; i < m; ++i) {
-        out[k] = buf[i];
-        k += buf[i] <= (uint32_t)rng;
-      }
-      p += m;
-    } else {
-      int i = 0;
-      for (; i < m && k < n; ++i) {
-        out[k] = buf[i];
-        k += buf[i] <= (uint32_t)rng;
-      }
-      p += i;
-    }
-  }
-  *pos = p;
-  return FDR_OK;
+  if (n_states < 0 || (n_states > 0 && (!frames || !probs))) return set_error(FDR_ERR_INVALID, "NULL pointer / bad Z");
+  atari::StrategiesCall sc{};
+  rc = lanes_args(lanes, n_lanes, P, &sc.lanes);
+  if (rc) return rc;
+  sc.n_act = d->n_act;
+  sc.n_lanes = n_lanes;
+  sc.n_states = n_states;
+  sc.frames = frames;
+  sc.bn_mean = d->bn_mean;
+  sc.bn_var = d->bn_var;
+  sc.probs = probs;
+  return atari::launch_strategies(sc, ws, ws_bytes, (hipStream_t)stream);
 }

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cfloat>
 
+#include "fdr_atari.h"
 #include "fdr_pack.h"
 
 namespace fdr {
@@ -295,41 +296,46 @@ int64_t num_params(int n_act) {
 
 constexpr uint64_t kFrameSalt = 0x4652414D45533031ull, kRewardSalt = 0x5245574152443031ull;
 
-int launch_rollout(int n_act, int envs, int T, uint64_t env_seed, const LanesArgs& lanes, int n_lanes, uint64_t seed,
-                   int jiggle, const float* bn_mean, const float* bn_var, double* ret, double* ent, int32_t* steps,
-                   double* norm2, int32_t* actions, float* probs, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  Layout L;
-  Args A{};
-  if (!make_layout(n_act, &L, &A.o)) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
-  const Plan p = plan(L, n_lanes, envs);
-  if (!ws || ws_bytes < p.total) return set_error(FDR_ERR_WORKSPACE, "atari workspace too small");
-  if (n_lanes == 0) return FDR_OK;
+// What the three launchers' StepArgs have in common: the plan's pack and feature regions, the BN running stats, n_act
+static void fill_common(StepArgs& a, const Layout& L, const Plan& p, void* ws, const float* bn_mean,
+                        const float* bn_var) {
   char* w = static_cast<char*>(ws);
-  StepArgs& a = A.s;
   a.pack = reinterpret_cast<float*>(w + p.pack);
   a.pack_stride = L.pack;
   a.bn_mean = bn_mean;
   a.bn_var = bn_var;
+  a.n_act = L.n_act;
+  a.feat = reinterpret_cast<float*>(w + p.feat);
+}
+
+int launch_rollout(const RolloutCall& c, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  Layout L;
+  Args A{};
+  if (!make_layout(c.n_act, &L, &A.o)) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
+  const int n_lanes = c.n_lanes, envs = c.envs;
+  const Plan p = plan(L, n_lanes, envs);
+  if (!ws || ws_bytes < p.total) return set_error(FDR_ERR_WORKSPACE, "atari workspace too small");
+  if (n_lanes == 0) return FDR_OK;
+  StepArgs& a = A.s;
+  fill_common(a, L, p, ws, c.bn_mean, c.bn_var);
   a.n_lanes = n_lanes;
   a.envs = envs;
-  a.n_act = n_act;
-  a.T = T;
-  a.lane_offset = lanes.lane_offset;
-  a.fkey = mix64(env_seed ^ kFrameSalt);
-  a.rkey = mix64(env_seed ^ kRewardSalt);
-  a.akey = mix64(seed);
-  a.feat = reinterpret_cast<float*>(w + p.feat);
-  a.ret = ret;
-  a.ent = ent;
-  a.actions = actions;
-  a.probs = probs;
-  a.deterministic = lanes.deterministic;
-  double* n2 = reinterpret_cast<double*>(w + p.n2);
-  int rc = impala::launch_prep(L, lanes, const_cast<float*>(a.pack), n2, n_lanes, stream);
+  a.T = c.T;
+  a.lane_offset = c.lanes.lane_offset;
+  a.fkey = mix64(c.env_seed ^ kFrameSalt);
+  a.rkey = mix64(c.env_seed ^ kRewardSalt);
+  a.akey = mix64(c.seed);
+  a.ret = c.ret;
+  a.ent = c.ent;
+  a.actions = c.actions;
+  a.probs = c.probs;
+  a.deterministic = c.lanes.deterministic;
+  double* n2 = reinterpret_cast<double*>(static_cast<char*>(ws) + p.n2);
+  int rc = impala::launch_prep(L, c.lanes, const_cast<float*>(a.pack), n2, n_lanes, stream);
   if (rc) return rc;
   const int64_t ne = (int64_t)n_lanes * envs;
   hipLaunchKernelGGL(impala::init_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, ne,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, ret, ent);
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, c.ret, c.ent);
   switch (envs) {
     case 1: rc = launch_steps<1>(L, A, stream); break;
     case 2: rc = launch_steps<2>(L, A, stream); break;
@@ -339,7 +345,7 @@ int launch_rollout(int n_act, int envs, int T, uint64_t env_seed, const LanesArg
   if (rc) return rc;
   const int64_t nmax = std::max<int64_t>(ne, n_lanes);
   hipLaunchKernelGGL(impala::finish_kernel, dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, stream, n_lanes, envs,
-                     T, 1, jiggle, a.akey, lanes.lane_offset, n2, p.nblk, ret, ent, steps, norm2);
+                     c.T, 1, c.jiggle, a.akey, c.lanes.lane_offset, n2, p.nblk, c.ret, c.ent, c.steps, c.norm2);
   return check_launch("atari finish");
 }
 
@@ -350,29 +356,26 @@ int64_t forward_workspace_bytes(int n_act, int n) {
   return plan(L, 1, n).total;
 }
 
-int launch_forward(int n_act, const float* theta, int n, const float* frames, const float* bn_mean,
-                   const float* bn_var, float* probs, float* feat, void* ws, int64_t ws_bytes, hipStream_t stream) {
+int launch_forward(const ForwardCall& c, void* ws, int64_t ws_bytes, hipStream_t stream) {
   Layout L;
   Args A{};
-  if (!make_layout(n_act, &L, &A.o)) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
+  if (!make_layout(c.n_act, &L, &A.o)) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
+  const int n = c.n;
   const Plan p = plan(L, 1, n);
   if (!ws || ws_bytes < p.total) return set_error(FDR_ERR_WORKSPACE, "atari forward workspace too small");
   if (n == 0) return FDR_OK;
-  char* w = static_cast<char*>(ws);
   LanesArgs lanes{};
-  lanes.base = theta;
+  lanes.base = c.theta;
   StepArgs& a = A.s;
-  a.pack = reinterpret_cast<float*>(w + p.pack);
-  a.pack_stride = 0;
-  a.bn_mean = bn_mean;
-  a.bn_var = bn_var;
+  fill_common(a, L, p, ws, c.bn_mean, c.bn_var);
+  a.pack_stride = 0;  // one pack: every frame is theta's
   a.n_lanes = n;
   a.envs = 1;
-  a.n_act = n_act;
-  a.frames = frames;
-  a.feat = feat ? feat : reinterpret_cast<float*>(w + p.feat);
-  a.probs = probs;
-  int rc = impala::launch_prep(L, lanes, const_cast<float*>(a.pack), reinterpret_cast<double*>(w + p.n2), 1, stream);
+  a.frames = c.frames;
+  if (c.feat) a.feat = c.feat;
+  a.probs = c.probs;
+  double* n2 = reinterpret_cast<double*>(static_cast<char*>(ws) + p.n2);
+  int rc = impala::launch_prep(L, lanes, const_cast<float*>(a.pack), n2, 1, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(atari_conv_kernel, dim3((n + 7) / 8 * 8), dim3(kThreads), 0, stream, L, A);
   hipLaunchKernelGGL((atari_core_kernel<1, impala::kForward>), dim3(n), dim3(impala::kCoreThreads), 0, stream, L, A);
@@ -392,32 +395,26 @@ int64_t strategies_workspace_bytes(int n_act, int n_lanes, int Z) {
   return plan(L, c, Z).total;
 }
 
-int launch_strategies(int n_act, const LanesArgs& lanes, int n_lanes, int Z, const float* frames, const float* bn_mean,
-                      const float* bn_var, float* probs, void* ws, int64_t ws_bytes, hipStream_t stream) {
+int launch_strategies(const StrategiesCall& c, void* ws, int64_t ws_bytes, hipStream_t stream) {
   Layout L;
   Args A{};
-  if (!make_layout(n_act, &L, &A.o)) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
+  if (!make_layout(c.n_act, &L, &A.o)) return set_error(FDR_ERR_UNSUPPORTED, "n_act must be in 1..32");
+  const int n_lanes = c.n_lanes, Z = c.n_states;
   const int chunk = std::min(n_lanes, kStratLanes);
   const Plan p = plan(L, chunk, Z);
   if (!ws || ws_bytes < p.total) return set_error(FDR_ERR_WORKSPACE, "atari strategies workspace too small");
   if (n_lanes == 0 || Z == 0) return FDR_OK;
-  char* w = static_cast<char*>(ws);
   StepArgs& a = A.s;
-  a.pack = reinterpret_cast<float*>(w + p.pack);
-  a.pack_stride = L.pack;
-  a.bn_mean = bn_mean;
-  a.bn_var = bn_var;
+  fill_common(a, L, p, ws, c.bn_mean, c.bn_var);
   a.envs = Z;
   a.T = Z;
-  a.n_act = n_act;
-  a.frames = frames;
+  a.frames = c.frames;
   a.shared_frames = 1;
-  a.feat = reinterpret_cast<float*>(w + p.feat);
-  double* n2 = reinterpret_cast<double*>(w + p.n2);
+  double* n2 = reinterpret_cast<double*>(static_cast<char*>(ws) + p.n2);
   for (int l0 = 0; l0 < n_lanes; l0 += chunk) {
     const int nl = std::min(chunk, n_lanes - l0);
-    LanesArgs la = lanes;
-    la.base = lanes.base + (int64_t)l0 * lanes.base_stride;
+    LanesArgs la = c.lanes;
+    la.base = c.lanes.base + (int64_t)l0 * c.lanes.base_stride;
     if (la.idx) la.idx += l0;
     if (la.sign) la.sign += l0;
     if (la.deterministic) la.deterministic += l0;
@@ -425,7 +422,7 @@ int launch_strategies(int n_act, const LanesArgs& lanes, int n_lanes, int Z, con
     int rc = impala::launch_prep(L, la, const_cast<float*>(a.pack), n2, nl, stream);
     if (rc) return rc;
     a.n_lanes = nl;
-    a.probs = probs + (int64_t)l0 * Z * n_act;
+    a.probs = c.probs + (int64_t)l0 * Z * c.n_act;
     hipLaunchKernelGGL(atari_conv_kernel, dim3((nl + 7) / 8 * 8 * Z), dim3(kThreads), 0, stream, L, A);
     hipLaunchKernelGGL((atari_core_kernel<1, impala::kForward>), dim3(nl * Z), dim3(impala::kCoreThreads), 0, stream,
                        L, A);

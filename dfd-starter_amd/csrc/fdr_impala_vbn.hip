@@ -21,6 +21,7 @@
 // BN2d(32), ReLU, Linear 2592->256, BN1d(256) -- the head after it feeds no statistic.  Parity: G16.
 #include <cfloat>
 
+#include "fdr_atari.h"
 #include "fdr_impala.h"
 
 namespace fdr {
@@ -505,8 +506,8 @@ AVbnPlan avbn_plan(int n) {
 
 int64_t vbn_workspace_bytes(int n) { return n < 0 ? -1 : avbn_plan(n).total; }
 
-int launch_vbn(const float* theta, int n, const float* frames, float momentum, float* bn_mean, float* bn_var, void* ws,
-               int64_t ws_bytes, hipStream_t s) {
+int launch_vbn(const VbnCall& c, void* ws, int64_t ws_bytes, hipStream_t s) {
+  const int n = c.n;
   const AVbnPlan pl = avbn_plan(n);
   if (!ws || ws_bytes < pl.total) return set_error(FDR_ERR_WORKSPACE, "atari bn refresh workspace too small");
   char* base = static_cast<char*>(ws);
@@ -517,18 +518,18 @@ int launch_vbn(const float* theta, int n, const float* frames, float momentum, f
   double* part = reinterpret_cast<double*>(base + pl.part);
   float* sc = reinterpret_cast<float*>(base + pl.scale);
   float* sh = reinterpret_cast<float*>(base + pl.shift);
-  const float* th = theta;
+  const float* th = c.theta;
   const int nb = n < impala::kStatBlocks ? n : impala::kStatBlocks;
   // statistics of a BN's input [n][C][HW] -> its running stats (at `at` in the flat [16 | 32 | 256]) + sc / sh
   auto bn_stats = [&](const float* in, int C, int HW, int64_t w, int at) {
     hipLaunchKernelGGL(stats_kernel, dim3(C, nb), dim3(256), 0, s, in, n, C, HW, 0, 1.f, part);
     hipLaunchKernelGGL(finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, C, nb, (int64_t)n * HW, part, th + w,
-                       th + w + C, momentum, bn_mean + at, bn_var + at, sc, sh);
+                       th + w + C, c.momentum, c.bn_mean + at, c.bn_var + at, sc, sh);
   };
   auto grid = [](int64_t total) { return dim3((unsigned)((total + 255) / 256)); };
   const int64_t t1 = (int64_t)n * kA1 * kO1 * kO1, t2 = (int64_t)n * kAFeat;
-  hipLaunchKernelGGL((sconv_kernel<4, kA1, 8, 4, 84, kO1, false>), grid(t1), dim3(256), 0, s, frames, nullptr, nullptr,
-                     th + kC1w, th + kC1b, X1, t1);
+  hipLaunchKernelGGL((sconv_kernel<4, kA1, 8, 4, 84, kO1, false>), grid(t1), dim3(256), 0, s, c.frames, nullptr,
+                     nullptr, th + kC1w, th + kC1b, X1, t1);
   bn_stats(X1, kA1, kO1 * kO1, kBn1, 0);
   hipLaunchKernelGGL((sconv_kernel<kA1, kA2, 4, 2, kO1, kO2, true>), grid(t2), dim3(256), 0, s, X1, sc, sh, th + kC2w,
                      th + kC2b, X2, t2);

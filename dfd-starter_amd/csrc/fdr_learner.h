@@ -1,0 +1,112 @@
+// Internal (non-ABI) host interface of the learner-side units behind the C ABI (fdr_api.hip): the launchers and
+// workspace queries of fdr_learner.hip, fdr_learner_fused.hip, fdr_dsgd.hip, fdr_novelty.hip and fdr_mlp_vbn.hip,
+// and the two structs that cross to their kernels by value (LambdaRow, FdArgs).
+#pragma once
+#include "fdr_internal.h"
+
+namespace fdr {
+
+// ---- fdr_learner.hip ----
+int launch_perturb(const float* theta, int64_t P, const float* table, int64_t table_size,
+                   const int64_t* idx, const int8_t* sign, int n, float sigma, float* out,
+                   hipStream_t stream);
+int launch_fd_weights(const double* r_all, int n_all, double pr, int lo, int n_local,
+                      const int8_t* sign, const double* n2, int lpd, float sigma, double* coef,
+                      hipStream_t stream);
+
+// The tiling of a noise-weighted gradient: 256-column blocks x row chunks, one f64 partial slab per chunk.  The
+// staged pair (grad_plan) and the fused kernel (fused_plan) choose rows_per_chunk by formulas of their own; each
+// fixes its summation order and with it the result bits.
+struct GradPlan {
+  int col_blocks, rows_per_chunk, n_chunks;
+};
+int64_t grad_workspace_bytes(int n_dirs, int64_t P);
+int launch_fd_grad(const float* table, int64_t table_size, const int64_t* idx, const double* coef,
+                   int n_dirs, int64_t P, double* g, void* ws, int64_t ws_bytes, hipStream_t stream);
+
+// Delayed-return perturbation rows (fdr_fd_lambda_norms / fdr_fd_grad_lambda), by value to kernels.
+struct LambdaRow {
+  const float* table;
+  int64_t max_idx;
+  const int64_t* idx;
+  const int8_t* sign;
+  const int32_t* slot;
+  const float* drift;
+  int n_slots;
+  int64_t P;
+  float sigma;
+
+  // pointer to eps_i (row 0 if the offset is out of range: the caller poisons that row with NaN)
+  __device__ __forceinline__ const float* eps(int i, bool& bad) const {
+    const int64_t off = idx[i];
+    bad = off < 0 || off > max_idx;
+    return table + (bad ? 0 : off);
+  }
+  __device__ __forceinline__ const float* dr(int i) const {
+    const int s = slot ? slot[i] : -1;
+    return (s >= 0 && s < n_slots) ? drift + (int64_t)s * P : nullptr;
+  }
+  __device__ __forceinline__ float value(const float* e, const float* d, int sg, int64_t p) const {
+#pragma clang fp contract(off)
+    float v = sigma * e[p];
+    v = sg < 0 ? -v : v;
+    return d ? v + d[p] : v;
+  }
+};
+int launch_lambda_norms(const LambdaRow& R, int n, double* n2, hipStream_t stream);
+int launch_lambda_grad(const LambdaRow& R, const double* coef, int n, double* g, void* ws, int64_t ws_bytes,
+                       hipStream_t stream);
+
+// ---- fdr_learner_fused.hip ----
+// fd_grad_fused_kernel's argument.  The caller fills the first block; launch_fd_grad_fused adds the plan and the
+// workspace regions.
+struct FdArgs {
+  const float* table;
+  int64_t max_idx;       // table_size - P: largest legal offset
+  const int64_t* idx;    // per LOCAL lane [n_dirs * lpd]; direction d's row starts at idx[d * lpd]
+  int n_dirs;
+  int64_t P;
+  const double* r_all;   // [n_all]; MOMENTS: the local lanes' rewards only
+  int n_all;             // lanes over all ranks
+  double pr;
+  int lo;                // this rank's first global lane
+  const int8_t* sign;    // [n_dirs * lpd] (local lanes)
+  const double* n2;      // [n_dirs * lpd]
+  const double* w;       // centred-rank weights of the local lanes
+  int lpd;
+  float sigma;
+  int rows_per_chunk, n_chunks, col_blocks;
+  double* partial;       // [n_chunks][P] (x2 in MOMENTS mode)
+  unsigned* cnt;         // [col_blocks] chunk tickets, [col_blocks] the DSGD ticket
+  double* out;           // g [P]; MOMENTS: [A | B | n_local | r' slots [n_all]]
+  double* gsq;           // [col_blocks] sum fl32(-g)^2 per column block (fdr_fd_step), or NULL
+};
+struct FusedCall {
+  FdArgs fd;             // table .. sigma and out
+  int mode;              // FDR_WEIGHT_*
+  // fdr_fd_step: DSGD in the same call (theta NULL: the gradient only)
+  float* theta;
+  double lr, lr_scale;
+  float* hist;           // theta_new also goes here (the learner's policy_history), or NULL
+  double* dsgd_out;      // [||d theta||, ||fl32(-g)||]
+};
+int64_t fused_workspace_bytes(int n_dirs, int n_local, int64_t P, int mode);
+int64_t fused_counter_bytes(int n_dirs, int64_t P);
+int launch_fd_grad_fused(const FusedCall& c, void* ws, int64_t ws_bytes, hipStream_t stream);
+int launch_rank_weights(const double* r_all, int n_all, int lo, int n_local, double* w, hipStream_t stream);
+
+// ---- fdr_dsgd.hip ----
+int64_t dsgd_workspace_bytes(int64_t P);
+int launch_dsgd_ex(float* theta, const double* src, int mom, int64_t P, double lr, double lr_scale, double* g_out,
+                   double* out, void* ws, int64_t ws_bytes, hipStream_t stream);
+
+// ---- fdr_novelty.hip ----
+int launch_strategy_dist(const float* S, int n, const float* B, int H, int Z, int D, int kind, double* dists,
+                         double* min_d, int32_t* arg, hipStream_t stream);
+
+// ---- fdr_mlp_vbn.hip ----
+int64_t bn_refresh_workspace_bytes(int n);
+int launch_bn_refresh(int n_in, const float* theta, const float* x, int n, float momentum, float* rm, float* rv,
+                      void* ws, int64_t ws_bytes, hipStream_t stream);
+
+}  // namespace fdr

@@ -78,3 +78,63 @@ def test_ctx_create_reports_missing_device():
     from fdr import _lib
     c = ctypes.c_void_p()
     assert _lib.lib.fdr_ctx_create(0, ctypes.byref(c)) == _lib.FDR_ERR_HIP
+
+
+def _atari_calls(lib):
+    """The four entry points that take an fdr_atari_desc, every other argument NULL / 0: the descriptor is checked
+    first, before any pointer is looked at."""
+    return {
+        "fdr_atari_rollout": lambda d: lib.fdr_atari_rollout(None, d, None, 0, 0, 0, None, None, None, None, None, None,
+                                                             None, 0, None),
+        "fdr_atari_forward": lambda d: lib.fdr_atari_forward(None, d, None, 0, None, None, None, None, 0, None),
+        "fdr_atari_bn_refresh": lambda d: lib.fdr_atari_bn_refresh(None, d, None, 0, None, 0.1, None, None, None, 0,
+                                                                   None),
+        "fdr_atari_strategies": lambda d: lib.fdr_atari_strategies(None, d, None, 0, 0, None, None, None, 0, None),
+    }
+
+
+@pytest.mark.parametrize("entry", ["fdr_atari_rollout", "fdr_atari_forward", "fdr_atari_bn_refresh",
+                                   "fdr_atari_strategies"])
+def test_atari_descriptor_validation_without_gpu(entry):
+    """NULL desc -> INVALID, n_act outside 1..32 -> UNSUPPORTED, n_params off by one -> INVALID, in that order and with
+    these texts, at every Atari entry point (no GPU needed: rejected before any device work)."""
+    from fdr import _lib
+    lib = _lib.lib
+    call = _atari_calls(lib)[entry]
+    P = lib.fdr_atari_num_params(6)
+    assert P > 0
+    assert call(None) == _lib.FDR_ERR_INVALID
+    assert lib.fdr_last_error() == b"atari desc is NULL"
+    for n_act in (0, 33):
+        d = _lib.AtariDesc(n_act, 2, 3, 0, 0, P, None, None)
+        assert call(ctypes.byref(d)) == _lib.FDR_ERR_UNSUPPORTED
+        assert lib.fdr_last_error() == b"n_act must be in 1..32"
+    for off in (-1, 1):
+        d = _lib.AtariDesc(6, 2, 3, 0, 0, P + off, None, None)
+        assert call(ctypes.byref(d)) == _lib.FDR_ERR_INVALID
+        assert lib.fdr_last_error() == b"n_params does not match the AtariPolicy layout"
+
+
+def test_atari_workspace_queries_reject_null_desc():
+    from fdr import _lib
+    assert _lib.lib.fdr_atari_workspace_bytes(None, 4) == -1
+    assert _lib.lib.fdr_atari_strategies_workspace_bytes(None, 300, 3) == -1
+
+
+def test_workspace_sizes_are_pinned():
+    """The byte counts the library reported before the learner / Atari host code was split into units (read from that
+    build): callers size their buffers with these queries, so a refactor of the plans must not move them."""
+    from fdr import _lib
+    lib = _lib.lib
+    assert lib.fdr_dsgd_workspace_bytes(6092) == 4160
+    assert lib.fdr_fd_grad_workspace_bytes(2048, 6092) == 1559552
+    assert lib.fdr_fd_grad_fused_workspace_bytes(2048, 2, 6092, _lib.FDR_WEIGHT_ZSCORE) == 1593088
+    assert lib.fdr_fd_grad_fused_workspace_bytes(2048, 2, 6092, _lib.FDR_WEIGHT_CENTERED_RANK) == 1593088
+    assert lib.fdr_fd_grad_fused_workspace_bytes(2048, 2, 6092, _lib.FDR_WEIGHT_MOMENTS) == 3152640
+    assert lib.fdr_fd_grad_fused_counter_bytes(2048, 6092) == 256
+    assert lib.fdr_bn_refresh_workspace_bytes(16) == 11520
+    P = lib.fdr_atari_num_params(6)
+    d = _lib.AtariDesc(6, 2, 3, 0, 0, P, None, None)   # 4 lanes x 2 envs per lane
+    assert lib.fdr_atari_workspace_bytes(ctypes.byref(d), 4) == 10962944
+    # 300 lanes: past the 256-lane chunk, so the plan is the chunk's, not the call's
+    assert lib.fdr_atari_strategies_workspace_bytes(ctypes.byref(d), 300, 3) == 704272384

@@ -262,18 +262,16 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
     return set_error(FDR_ERR_INVALID, "obs_mean and obs_std must both be given or both NULL");
   if (env->episode_len <= 0 || env->episode_len >= (1 << 28))
     return set_error(FDR_ERR_INVALID, "episode_len out of range");
-  if (env->kind == FDR_ENV_CARTPOLE || env->kind == FDR_ENV_PENDULUM) {
+  const PhysicsEnv* const pe = physics_env(env->kind);
+  if (pe) {
     // the descriptor on its own first (INVALID), then the policy it is paired with (UNSUPPORTED)
-    const bool cart = env->kind == FDR_ENV_CARTPOLE;
     if (env->M || env->K || env->s0 || env->walkable)
       return set_error(FDR_ERR_INVALID, "physics envs take no M, K, s0 or walkable");
     if (env->done_threshold != 0.f) return set_error(FDR_ERR_INVALID, "physics envs take done_threshold 0");
-    if (env->obs_dim != (cart ? 4 : 3) || env->act_dim != (cart ? 2 : 1))
-      return set_error(FDR_ERR_INVALID, "CartPole is obs 4 / act 2, Pendulum obs 3 / act 1");
+    if (env->obs_dim != pe->obs || env->act_dim != pe->act)
+      return set_error(FDR_ERR_INVALID, "obs_dim / act_dim are not this physics env's own");
     if (env->episode_len > 10000) return set_error(FDR_ERR_INVALID, "physics env episode_len must be 1 .. 10000");
-    if (k.discrete != cart || k.n_in != env->obs_dim || k.n_act != env->act_dim)
-      return set_error(FDR_ERR_UNSUPPORTED,
-                       cart ? "CartPole needs a DiscretePolicy(4, 2)" : "Pendulum needs a MujocoPolicy(3, 1)");
+    if (!physics_policy_ok(*pe, k)) return set_error(FDR_ERR_UNSUPPORTED, pe->policy_msg);
   }
   if (env->obs_dim != k.n_in || env->act_dim != k.n_act)
     return set_error(FDR_ERR_INVALID, "env obs/act dims do not match the policy");
@@ -288,7 +286,7 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
       return set_error(FDR_ERR_INVALID, "trap env needs the walkable map");
     if (!k.discrete || k.n_in != 2 || k.n_act != 9)
       return set_error(FDR_ERR_INVALID, "trap env needs a DiscretePolicy(2, 9)");
-  } else if (env->kind == FDR_ENV_CARTPOLE || env->kind == FDR_ENV_PENDULUM) {
+  } else if (pe) {
     // validated above
   } else {
     return set_error(FDR_ERR_INVALID, "unknown env kind");

@@ -112,7 +112,29 @@ int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const R
 // synthetic env, one lane per wave: the 128-VGPR kernel / the 256-VGPR one
 int launch_rollout_lane(const PolicyKey& k, const RolloutArgs& args, hipStream_t stream);
 int launch_rollout_wide(const PolicyKey& k, const RolloutArgs& args, hipStream_t stream);
-// trap gridworld, CartPole, Pendulum
+// The classic-control physics envs: each kind with its own observation / action sizes and the one policy it runs
+// under.  fdr_rollout_ex validates the descriptor against this table and launch_rollout_env the policy.
+struct PhysicsEnv {
+  int kind, obs, act;
+  bool discrete;
+  const char* policy_msg;
+};
+constexpr PhysicsEnv kPhysicsEnvs[] = {
+    {FDR_ENV_CARTPOLE, 4, 2, true, "CartPole needs a DiscretePolicy(4, 2)"},
+    {FDR_ENV_PENDULUM, 3, 1, false, "Pendulum needs a MujocoPolicy(3, 1)"},
+    {FDR_ENV_ACROBOT, 6, 3, true, "Acrobot needs a DiscretePolicy(6, 3)"},
+    {FDR_ENV_MOUNTAINCAR, 2, 3, true, "MountainCar needs a DiscretePolicy(2, 3)"},
+    {FDR_ENV_MOUNTAINCAR_CONT, 2, 1, false, "MountainCarContinuous needs a MujocoPolicy(2, 1)"},
+};
+inline const PhysicsEnv* physics_env(int kind) {  // NULL: not a physics env
+  for (const PhysicsEnv& e : kPhysicsEnvs)
+    if (e.kind == kind) return &e;
+  return nullptr;
+}
+inline bool physics_policy_ok(const PhysicsEnv& e, const PolicyKey& k) {
+  return k.discrete == e.discrete && k.n_in == e.obs && k.n_act == e.act;
+}
+// trap gridworld and the physics envs
 int launch_rollout_env(const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream);
 // two lanes per wave; round_lanes: lanes of one resident round (more go out as consecutive launches)
 int launch_rollout_pair(const PolicyKey& k, const RolloutArgs& args, int round_lanes, hipStream_t stream);

@@ -145,10 +145,14 @@ struct ShapeList {};
 // every kernel family: forward, both loaders, rollout_kernel (synthetic env, one-lane and WIDE), rollout_pair_kernel
 using MlpShapes = ShapeList<Shape<2, 9, true>, Shape<4, 2, true>, Shape<8, 4, true>, Shape<17, 6, false>,
                             Shape<11, 3, false>, Shape<8, 2, false>>;
-// Shapes only the physics envs use (Pendulum's MujocoPolicy(3, 1)): the one-lane rollout of their env, the batched
+// Shapes only the physics envs use (Pendulum's MujocoPolicy(3, 1), Acrobot's DiscretePolicy(6, 3), MountainCar's
+// DiscretePolicy(2, 3), MountainCarContinuous's MujocoPolicy(2, 1)): the one-lane rollout of their env, the batched
 // forward and the lane loader's read-back -- no synthetic-env, pair or WIDE instance
-using PhysicsShapes = ShapeList<Shape<3, 1, false>>;
+using PhysicsShapes = ShapeList<Shape<3, 1, false>, Shape<6, 3, true>, Shape<2, 3, true>, Shape<2, 1, false>>;
 static_assert(Layout<3, 1, false>::P == 4546, "MujocoPolicy(3, 1) has 4546 parameters");
+static_assert(Layout<6, 3, true>::P == 5071, "DiscretePolicy(6, 3) has 5071 parameters");
+static_assert(Layout<2, 3, true>::P == 4807, "DiscretePolicy(2, 3) has 4807 parameters");
+static_assert(Layout<2, 1, false>::P == 4482, "MujocoPolicy(2, 1) has 4482 parameters");
 
 template <class S, class... T>
 constexpr bool shape_in(ShapeList<T...>) {
@@ -195,7 +199,7 @@ constexpr int kFeatTerm = 16;     // terminating synthetic env (fdr_env_desc.don
 constexpr int kLaneFeatBits = kFeatStates | kFeatObsStats | kFeatObsNorm | kFeatInject | kFeatTerm;  // 24 sets
 constexpr int kWideFeatBits = kFeatStates | kFeatObsStats | kFeatObsNorm | kFeatTerm;                // 16: no u_inject
 constexpr int kPairFeatBits = kFeatStates | kFeatObsNorm | kFeatTerm;                                //  8
-// physics envs: no kFeatTerm (CartPole's termination lives under its ENV branch)
+// physics envs: no kFeatTerm (each env's termination lives under its ENV branch)
 constexpr int kPhysicsFeatBits = kFeatStates | kFeatObsStats | kFeatObsNorm | kFeatInject;           // 12
 constexpr bool feat_legal(int family_bits, int f) {
   return (f & ~family_bits) == 0 && (f & (kFeatInject | kFeatObsStats)) != (kFeatInject | kFeatObsStats);

@@ -11,8 +11,8 @@
 //   * Activations cross lanes through a 1 KiB per-wave LDS scratch (one ds_write_b32 per lane,
 //     broadcast ds_read_b128 back) feeding packed f32 FMAs, or through DPP row_newbcast where the
 //     input already sits in the caller's 16-lane row (the head, K a).
-//   * The env (synthetic linear-tanh system, the trap gridworld, or CartPole-v1 / Pendulum-v1 physics) runs inside
-//     the same loop.
+//   * The env (synthetic linear-tanh system, the trap gridworld, or one of gym's five classic-control systems) runs
+//     inside the same loop.
 //   * 4 lanes (waves) per 256-thread workgroup, <= 128 VGPRs -> 16 waves/CU: 4096 lanes fill
 //     all 256 CUs in one wave of workgroups.
 //
@@ -20,7 +20,7 @@
 // kernels and the Welford merge.  The rollout kernels are compiled in units of their own, one family each:
 //   fdr_rollout_lane.hip   rollout_kernel, synthetic env          (fdr_rollout_kernel.h, fdr_mlp_lane.h)
 //   fdr_rollout_wide.hip   rollout_kernel<WIDE>, synthetic env
-//   fdr_rollout_env.hip    rollout_kernel, trap / CartPole / Pendulum
+//   fdr_rollout_env.hip    rollout_kernel, trap / CartPole / Pendulum / Acrobot / MountainCar (both)
 //   fdr_rollout_pair.hip   rollout_pair_kernel                    (fdr_mlp_pair.h)
 // fdr_mlp.h holds what they share: Layout, the compiled shapes (with_shape) and the feature bits.
 #include "fdr_mlp_lane.h"

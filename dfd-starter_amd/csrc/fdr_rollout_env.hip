@@ -1,34 +1,43 @@
 // fdr_rollout_env.hip -- the rollout_kernel instances of the envs that are not the synthetic one: the trap
-// gridworld at DiscretePolicy(2, 9), CartPole-v1 at DiscretePolicy(4, 2), Pendulum-v1 at MujocoPolicy(3, 1).
-// Always the one-lane kernel, whatever the context's rollout_impl says.
+// gridworld at DiscretePolicy(2, 9), CartPole-v1 at DiscretePolicy(4, 2), Pendulum-v1 at MujocoPolicy(3, 1),
+// Acrobot-v1 at DiscretePolicy(6, 3), MountainCar-v0 at DiscretePolicy(2, 3), MountainCarContinuous-v0 at
+// MujocoPolicy(2, 1).  Always the one-lane kernel, whatever the context's rollout_impl says.
 #include "fdr_rollout_kernel.h"
 
 namespace fdr {
 
+// The physics env ENV at its one shape (NIN, NA, DISC): launched when S is that shape and env_kind that env.
+template <class S, int ENV, int NIN, int NA, bool DISC>
+bool launch_physics(int env_kind, const RolloutArgs& args, int feat, hipStream_t stream, const char* what, int& rc) {
+  if constexpr (S::NIN == NIN && S::NA == NA && S::DISC == DISC) {
+    if (env_kind == ENV) {
+      rc = launch_rollout_kernel<S, ENV, false, kPhysicsFeatBits>(args, feat, stream, what,
+                                                                  "u_inject is not combined with the obs statistics");
+      return true;
+    }
+  }
+  return false;
+}
+
 int launch_rollout_env(const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream) {
   // physics envs: one policy shape each
-  if (env_kind == FDR_ENV_CARTPOLE && (k.n_in != 4 || k.n_act != 2 || !k.discrete))
-    return set_error(FDR_ERR_UNSUPPORTED, "CartPole needs a DiscretePolicy(4, 2)");
-  if (env_kind == FDR_ENV_PENDULUM && (k.n_in != 3 || k.n_act != 1 || k.discrete))
-    return set_error(FDR_ERR_UNSUPPORTED, "Pendulum needs a MujocoPolicy(3, 1)");
-  const bool physics = env_kind == FDR_ENV_CARTPOLE || env_kind == FDR_ENV_PENDULUM;
+  const PhysicsEnv* const pe = physics_env(env_kind);
+  if (pe && !physics_policy_ok(*pe, k)) return set_error(FDR_ERR_UNSUPPORTED, pe->policy_msg);
   const char* const no_shape = "no compiled rollout for this (kind, n_in, n_act)";
   auto launch = [&](auto shape) {
     using S = decltype(shape);
-    // no kFeatTerm: CartPole's termination lives under its ENV branch.  u_inject never comes with the Welford
+    // no kFeatTerm: a physics env's termination lives under its ENV branch.  u_inject never comes with the Welford
     // statistics (fdr_rollout_ex refuses it).
     const int feat = rollout_feat(args, false);
-    const char* const no_feat = "u_inject is not combined with the obs statistics";
-    if constexpr (S::NIN == 4 && S::NA == 2 && S::DISC) {
-      if (env_kind == FDR_ENV_CARTPOLE)
-        return launch_rollout_kernel<S, FDR_ENV_CARTPOLE, false, kPhysicsFeatBits>(args, feat, stream,
-                                                                                   "rollout_kernel<cartpole>", no_feat);
-    }
-    if constexpr (S::NIN == 3 && S::NA == 1 && !S::DISC) {
-      if (env_kind == FDR_ENV_PENDULUM)
-        return launch_rollout_kernel<S, FDR_ENV_PENDULUM, false, kPhysicsFeatBits>(args, feat, stream,
-                                                                                   "rollout_kernel<pendulum>", no_feat);
-    }
+    int rc = FDR_OK;
+    if (launch_physics<S, FDR_ENV_CARTPOLE, 4, 2, true>(env_kind, args, feat, stream, "rollout_kernel<cartpole>", rc) ||
+        launch_physics<S, FDR_ENV_PENDULUM, 3, 1, false>(env_kind, args, feat, stream, "rollout_kernel<pendulum>", rc) ||
+        launch_physics<S, FDR_ENV_ACROBOT, 6, 3, true>(env_kind, args, feat, stream, "rollout_kernel<acrobot>", rc) ||
+        launch_physics<S, FDR_ENV_MOUNTAINCAR, 2, 3, true>(env_kind, args, feat, stream,
+                                                           "rollout_kernel<mountaincar>", rc) ||
+        launch_physics<S, FDR_ENV_MOUNTAINCAR_CONT, 2, 1, false>(env_kind, args, feat, stream,
+                                                                 "rollout_kernel<mountaincar_cont>", rc))
+      return rc;
     if constexpr (S::NIN == 2 && S::NA == 9 && S::DISC) {
       if (env_kind == FDR_ENV_TRAP)
         return launch_rollout_kernel<S, FDR_ENV_TRAP, false, kLaneFeatBits>(
@@ -36,7 +45,7 @@ int launch_rollout_env(const PolicyKey& k, int env_kind, const RolloutArgs& args
     }
     return set_error(FDR_ERR_UNSUPPORTED, "env kind not compiled for this policy shape");
   };
-  return physics ? with_shape<true>(k, no_shape, launch) : with_shape<false>(k, no_shape, launch);
+  return pe ? with_shape<true>(k, no_shape, launch) : with_shape<false>(k, no_shape, launch);
 }
 
 }  // namespace fdr

@@ -21,6 +21,12 @@ into the rollout kernel, so an env here is a *descriptor*: device tensors + shap
   (unscaled) action to [-2, 2], pays -(theta^2 + 0.1 thetadot^2 + 0.001 u^2) and always runs to the limit.  Pure
   descriptors: they own no device tensors.  ``make_env(..., physics=True)`` returns them; by default the CartPole /
   Pendulum ids keep mapping to ``SyntheticEnv`` shapes.
+* ``AcrobotEnv`` / ``MountainCarEnv`` / ``MountainCarContinuousEnv`` -- the rest of gym's classic-control family, same
+  kernel, same per-lane resets (Acrobot U(-0.1, 0.1)^4; MountainCar position U(-0.6, -0.4) at rest).  All three end
+  early on SUCCESS: Acrobot (one RK4 step of 0.2 s of the "book" dynamics per action, torque action - 1) pays -1 per
+  step and 0 on the step that swings its free end above the goal height; MountainCar-v0 pays -1 per step taken until
+  position >= 0.5; MountainCarContinuous-v0 clamps the action to [-1, 1] for the force, charges 0.1 a^2 of the
+  unclamped action and pays +100 on the step that reaches position >= 0.45.
 * ``StackedFrameEnv`` -- the same hash frames as 4 x 84 x 84 stacks for AtariPolicy (fdr_atari_rollout).
 * ``FrameEnv`` -- the Atari/procgen-shaped workload of BASELINE configs 4/5 for ImpalaPolicy:
   uint8-valued 3x64x64 frames from a counter hash of (env, t, pixel), a +1/-1/0 reward for hitting
@@ -138,6 +144,33 @@ class PendulumEnv(_PhysicsEnv):
     obs_dim, act_dim, discrete, terminates = 3, 1, False, False
 
     def __init__(self, episode_len=200):
+        super().__init__(episode_len)
+
+
+class AcrobotEnv(_PhysicsEnv):
+    """gym Acrobot-v1, DiscretePolicy(6, 3) (obs cos / sin of both angles, both velocities); ends on success."""
+    kind = _lib.FDR_ENV_ACROBOT
+    obs_dim, act_dim, discrete, terminates = 6, 3, True, True
+
+    def __init__(self, episode_len=500):
+        super().__init__(episode_len)
+
+
+class MountainCarEnv(_PhysicsEnv):
+    """gym MountainCar-v0, DiscretePolicy(2, 3) (obs position, velocity); ends on success."""
+    kind = _lib.FDR_ENV_MOUNTAINCAR
+    obs_dim, act_dim, discrete, terminates = 2, 3, True, True
+
+    def __init__(self, episode_len=200):
+        super().__init__(episode_len)
+
+
+class MountainCarContinuousEnv(_PhysicsEnv):
+    """gym MountainCarContinuous-v0, MujocoPolicy(2, 1) (obs position, velocity); ends on success (+100)."""
+    kind = _lib.FDR_ENV_MOUNTAINCAR_CONT
+    obs_dim, act_dim, discrete, terminates = 2, 1, False, True
+
+    def __init__(self, episode_len=999):
         super().__init__(episode_len)
 
 

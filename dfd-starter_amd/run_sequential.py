@@ -15,8 +15,9 @@ per-episode host loop replaced by ONE batched rollout launch per epoch:
 ``antithetic=True`` evaluates +eps/-eps pairs (build extension; batch_size then counts directions).
 Environments are GPU-resident (envs/): the trap env exactly, MuJoCo / CartPole ids map to the
 build's synthetic fixed-length envs of the same shapes (no simulator exists on this platform);
-``physics=True`` instead runs CartPole-v1 / -v0 and Pendulum ids on the kernel's own classic-control dynamics
-(envs.CartPoleEnv / PendulumEnv: gym's formulas, per-lane random resets, CartPole's early termination).
+``physics=True`` instead runs CartPole-v1 / -v0, Pendulum ids, Acrobot-v1, MountainCar-v0 and
+MountainCarContinuous-v0 on the kernel's own classic-control dynamics (envs.CartPoleEnv / PendulumEnv / AcrobotEnv /
+MountainCarEnv / MountainCarContinuousEnv: gym's formulas, per-lane random resets, early termination).
 ``procgen`` ids (the reference's ImpalaPolicy route, run_sequential.py:68-71) and Atari ``NoFrameskip``
 ids (BASELINE configs 4/5: the Impala conv stack on Atari-shaped frames) run ImpalaPolicy on the
 synthetic frame env (``envs_per_lane`` envs per perturbation, ``fp16`` rollouts for config 5), with the
@@ -31,7 +32,8 @@ import torch
 
 from dsgd import DSGD
 from fdr import engine
-from envs import CartPoleEnv, FrameEnv, PendulumEnv, StackedFrameEnv, SyntheticEnv, TrapEnv
+from envs import (AcrobotEnv, CartPoleEnv, FrameEnv, MountainCarContinuousEnv, MountainCarEnv, PendulumEnv,
+                  StackedFrameEnv, SyntheticEnv, TrapEnv)
 from learner import FDBatch, FDState, FiniteDifferences
 from policies import AtariPolicy, DiscretePolicy, ImpalaPolicy, MujocoPolicy
 from strategy import StrategyHandler
@@ -48,17 +50,23 @@ def frame_env_id(env_id):
     return "procgen" in env_id or "NoFrameskip" in env_id
 
 
-PHYSICS_IDS = "CartPole-v1, CartPole-v0, Pendulum*"
+PHYSICS_IDS = "CartPole-v1, CartPole-v0, Pendulum*, Acrobot-v1, MountainCar-v0, MountainCarContinuous-v0"
+# the ids that name exactly one env and time limit
+PHYSICS_ENVS = {"Acrobot-v1": (AcrobotEnv, 500), "MountainCar-v0": (MountainCarEnv, 200),
+                "MountainCarContinuous-v0": (MountainCarContinuousEnv, 999)}
 
 
 def make_physics_env(env_id, episode_len=None):
-    """The classic-control envs the rollout kernel steps for real (envs.CartPoleEnv / PendulumEnv)."""
+    """The classic-control envs the rollout kernel steps for real (envs._PhysicsEnv subclasses)."""
     if env_id == "CartPole-v1":
         return CartPoleEnv(500 if episode_len is None else episode_len)
     if env_id == "CartPole-v0":
         return CartPoleEnv(200 if episode_len is None else episode_len)
     if env_id.startswith("Pendulum"):
         return PendulumEnv(200 if episode_len is None else episode_len)
+    if env_id in PHYSICS_ENVS:
+        cls, T = PHYSICS_ENVS[env_id]
+        return cls(T if episode_len is None else episode_len)
     raise ValueError("physics=True supports the env ids %s (got %r)" % (PHYSICS_IDS, env_id))
 
 

@@ -52,6 +52,16 @@ typedef void* fdr_stream; /* hipStream_t */
                               its bounds (reward 1 per step taken) or at episode_len */
 #define FDR_ENV_PENDULUM 3 /* Pendulum-v1: obs 3 (cos, sin, thetadot) / 1 action dim, FDR_POLICY_MUJOCO; the action is
                               clamped to [-2, 2]; always runs episode_len steps */
+/* The rest of gym's classic_control family (added within fdr 0.5: three constants, no new export, same descriptor
+   rules).  All three end early on success. */
+#define FDR_ENV_ACROBOT 4 /* Acrobot-v1 ("book" dynamics, one RK4 step of 0.2 s): obs 6 (cos / sin of both angles, both
+                             velocities) / 3 actions (torque -1, 0, +1), FDR_POLICY_DISCRETE; reward -1 per step, 0 on
+                             the step that swings the free end above the goal height, which ends the episode */
+#define FDR_ENV_MOUNTAINCAR 5 /* MountainCar-v0: obs 2 (position, velocity) / 3 actions, FDR_POLICY_DISCRETE; reward -1
+                                 per step taken; ends at position >= 0.5 */
+#define FDR_ENV_MOUNTAINCAR_CONT 6 /* MountainCarContinuous-v0: obs 2 / 1 action dim, FDR_POLICY_MUJOCO; the force is
+                                      the action clamped to [-1, 1], the reward -0.1 a^2 of the unclamped action, +100
+                                      on the step that reaches position >= 0.45, which ends the episode */
 
 typedef struct fdr_policy_desc {
   int32_t kind;     /* FDR_POLICY_* */

@@ -1,0 +1,72 @@
+"""Learning measurement on the physics envs (DESIGN.md 7's tables; a measurement, no bar): SequentialRunner(physics=True,
+batch_size=2048, antithetic=True) with the reference's hyperparameters for 300 epochs, once per weighting.  "train" is
+the mean return of the epoch's sampled training lanes averaged over the 10 epochs before the row, "eval" the mean return
+over 64 deterministic lanes of theta from 64 different resets, "done" the share of those 64 that reached the goal.
+
+    python tools/physics_learning.py [env_id ...] [--epochs 300]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "dfd-starter_amd")):
+    sys.path.insert(0, p)
+
+from run_sequential import SequentialRunner  # noqa: E402
+
+IDS = ["Acrobot-v1", "MountainCar-v0", "MountainCarContinuous-v0"]
+
+
+def run(env_id, weighting, epochs, every):
+    r = SequentialRunner(env_id=env_id, physics=True, batch_size=2048, antithetic=True, verbose=False)
+    r.learner.weighting = weighting
+    launch = r.worker.launch
+    train, rows = [], []
+
+    def evaluate(epoch):
+        n = 64
+        res = launch(np.zeros(n, np.int64), np.zeros(n, np.int8), np.ones(n, np.int8), seed=100000 + epoch,
+                     jiggle=False)[0]
+        ret, steps = res.reward.cpu().numpy(), res.timesteps.cpu().numpy()
+        recent = np.mean(train[-10:]) if train else float("nan")
+        rows.append((epoch, recent, float(ret.mean()), float((steps < r.env.episode_len).mean())))
+
+    def spy(idx, sign, det, **kw):
+        if len(train) % every == 0:
+            evaluate(len(train))
+        out = launch(idx, sign, det, **kw)
+        train.append(float(out[0].reward[torch.as_tensor(sign != 0, device=out[0].reward.device)].mean().item()))
+        return out
+    r.worker.launch = spy
+    t0 = time.perf_counter()
+    r.train(epochs)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    evaluate(epochs)
+    return rows, wall
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("env_ids", nargs="*", default=IDS)
+    ap.add_argument("--epochs", type=int, default=300)
+    ap.add_argument("--every", type=int, default=50)
+    a = ap.parse_args()
+    for env_id in a.env_ids:
+        res = {w: run(env_id, w, a.epochs, a.every) for w in ("zscore", "centred_rank")}
+        print("%s: %d epochs, wall %.1f s (z-score) / %.1f s (centred rank)"
+              % (env_id, a.epochs, res["zscore"][1], res["centred_rank"][1]))
+        print("| epoch | z-score: train | z-score: eval (done) | centred rank: train | centred rank: eval (done) |")
+        print("|---|---|---|---|---|")
+        for z, c in zip(res["zscore"][0], res["centred_rank"][0]):
+            print("| %d | %.1f | %.1f (%.0f %%) | %.1f | %.1f (%.0f %%) |"
+                  % (z[0], z[1], z[2], 100 * z[3], c[1], c[2], 100 * c[3]), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -76,37 +76,57 @@ __device__ __forceinline__ T wave_sum(T v) {
 // discarded by the select), so every element's two loads are unconditional and the compiler batches them.  (r12: a
 // per-element `if (sgn != 0)` around the eps load put each load behind its own exec branch and wait -- ~200 serialised
 // HBM round trips per thread in the MLP rollouts' prologue.)
+//
+// The sign rides on sigma (ss = sgn < 0 ? -sigma : sigma, set once in LanesArgs::src), so an element costs one
+// product, one 32-bit select, one add and one f64 FMA instead of two sums, four selects and an f64 multiply and add
+// (the MLP rollouts' prologue is VALU-issue-bound: DESIGN.md 3.0).  With st = fl32(ss * eps[p]) and
+// z = sgn != 0 ? st : -0.0f the result is base[p] + z and the norm term fma(z, z, n2) in f64.  Same bits as the
+// two-sided form (tests/test_theta_prime_identities.py checks each identity in numpy):
+//   - fl32((-sigma) * eps) = -fl32(sigma * eps): round-to-nearest-even is symmetric about zero;
+//   - t - x and t + (-x) are the same IEEE operation, signed zeros included, so base[p] + z is t +/- st;
+//   - t + (-0.0f) = t for every t, -0.0f included (t + (+0.0f) would turn a -0.0f into +0.0f): an unperturbed lane
+//     gets t itself;
+//   - d = (double)z has a 24-bit significand, so d * d is exact in f64 and fma(d, d, n2) = fl64(n2 + d * d) is the
+//     rounded sum n2 + fl64(d * d) of the two-step form;
+//   - an unperturbed lane has d = -0.0, d * d = +0.0: the two-step form's n2 += 0.0;
+//   - a lane whose n2 starts as NaN (out-of-range offset) keeps it.
+// (A second form without the select, taken by waves that hold no unperturbed lane, was measured and not kept:
+// DESIGN.md 3.0 p14.)
 struct ParamSrc {
   const float* base;
   const float* eps;  // table + idx, or base (unperturbed lane: loaded, not used)
-  float sigma;
+  float ss;          // sigma with the lane's sign: -sigma when sgn < 0
   int sgn;           // +1 / -1 / 0
   double n2;         // running sum of fl32(sigma*eps)^2 over the elements this thread loaded
 
+  __device__ __forceinline__ float step(int64_t p) const {  // z: the signed step, -0.0f on an unperturbed lane
+#pragma clang fp contract(off)
+    const float st = ss * eps[p];
+    return sgn != 0 ? st : -0.0f;
+  }
   __device__ __forceinline__ float get(int64_t p) {
 #pragma clang fp contract(off)
     const float t = base[p];
-    const float st = sigma * eps[p];
-    const double d = (double)st;
-    n2 += sgn != 0 ? d * d : 0.0;
-    return sgn > 0 ? t + st : (sgn < 0 ? t - st : t);
+    const float z = step(p);
+    const double d = (double)z;
+    n2 = __builtin_fma(d, d, n2);
+    return t + z;
   }
   // get(p) counted in n2 only when `use` (an element read unconditionally from a clamped index whose value the caller
   // discards otherwise: no load behind a branch)
   __device__ __forceinline__ float get_if(int64_t p, bool use) {
 #pragma clang fp contract(off)
     const float t = base[p];
-    const float st = sigma * eps[p];
-    const double d = (double)st;
-    n2 += (use && sgn != 0) ? d * d : 0.0;
-    return sgn > 0 ? t + st : (sgn < 0 ? t - st : t);
+    const float z = step(p);
+    const double d = (double)(use ? z : -0.0f);
+    n2 = __builtin_fma(d, d, n2);
+    return t + z;
   }
   // same value, but not counted in n2 (an element several threads replicate)
   __device__ __forceinline__ float get_nocount(int64_t p) const {
 #pragma clang fp contract(off)
     const float t = base[p];
-    const float st = sigma * eps[p];
-    return sgn > 0 ? t + st : (sgn < 0 ? t - st : t);
+    return t + step(p);
   }
 };
 

@@ -50,7 +50,7 @@ struct LanesArgs {
   __device__ __forceinline__ ParamSrc src(int lane) const {
     ParamSrc s;
     s.base = base + (int64_t)lane * base_stride;
-    s.sigma = sigma;
+    s.ss = sigma;
     s.n2 = 0.0;
     s.sgn = 0;
     s.eps = s.base;  // unperturbed: a readable address whose value ParamSrc discards
@@ -61,6 +61,7 @@ struct LanesArgs {
         s.n2 = __builtin_nan("");
       } else if (sg != 0) {
         s.sgn = sg > 0 ? 1 : -1;
+        s.ss = sg > 0 ? sigma : -sigma;  // the sign rides on sigma (ParamSrc)
         s.eps = table + off;
       }
     }

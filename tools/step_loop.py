@@ -34,8 +34,10 @@ def loops(body):
 def main(path, pat, marker, dump=False):
     name, body = body_of(path, pat)
     cand = [(sum(marker in body[j] for j in range(a, b)), a, b) for a, b in loops(body)]
-    top = max(n for n, _, _ in cand)  # the unrolled main body, not a remainder loop
-    _, a, b = min((c for c in cand if c[0] == top), key=lambda c: c[2] - c[1])
+    # the unrolled main body: not a remainder loop (fewer markers), nor a region that wraps the body together with
+    # out-of-line prologue blocks and the remainder (more markers, but less than twice the body's)
+    top = max(n for n, _, _ in cand)
+    _, a, b = min((c for c in cand if 2 * c[0] > top), key=lambda c: c[2] - c[1])
     steps = top // int(sys.argv[4]) if len(sys.argv) > 4 and sys.argv[4].isdigit() else 1
     ins = [x for x in body[a:b + 1] if not x.startswith((".", ";")) and not x.endswith(":")]
     c = Counter(x.split()[0] for x in ins)

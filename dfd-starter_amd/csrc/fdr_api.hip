@@ -38,7 +38,9 @@ Context& default_context() {
     c->rollout_impl = !e ? FDR_ROLLOUT_AUTO
                          : strcmp(e, "single") == 0 ? FDR_ROLLOUT_SINGLE
                          : strcmp(e, "wide") == 0   ? FDR_ROLLOUT_WIDE
-                                                    : strcmp(e, "pair") == 0 ? FDR_ROLLOUT_PAIR : FDR_ROLLOUT_AUTO;
+                         : strcmp(e, "pair") == 0   ? FDR_ROLLOUT_PAIR
+                         : strcmp(e, "generic") == 0 ? FDR_ROLLOUT_GENERIC
+                                                     : FDR_ROLLOUT_AUTO;
     return c;
   }();
   return *d;
@@ -61,7 +63,7 @@ static int policy_key(const fdr_policy_desc* p, PolicyKey* k) {
   k->n_act = p->n_act;
   k->discrete = p->kind == FDR_POLICY_DISCRETE;
   k->n_params = p->n_params;
-  return FDR_OK;
+  return dyn_shape_check(*k);  // the widest limits any kernel family has (the runtime-shaped one's)
 }
 
 static int lanes_args(const fdr_lanes_desc* l, int n_lanes, int64_t P, LanesArgs* out) {
@@ -128,7 +130,8 @@ const char* fdr_version(void) { return "fdr 0.5 gfx950"; }
 const char* fdr_last_error(void) { return g_err.c_str(); }
 
 static int set_impl(Context& c, int32_t impl) {
-  if (impl != FDR_ROLLOUT_PAIR && impl != FDR_ROLLOUT_SINGLE && impl != FDR_ROLLOUT_AUTO && impl != FDR_ROLLOUT_WIDE)
+  if (impl != FDR_ROLLOUT_PAIR && impl != FDR_ROLLOUT_SINGLE && impl != FDR_ROLLOUT_AUTO && impl != FDR_ROLLOUT_WIDE &&
+      impl != FDR_ROLLOUT_GENERIC)
     return set_error(FDR_ERR_INVALID, "unknown rollout impl");
   c.rollout_impl = impl;
   return FDR_OK;
@@ -197,7 +200,7 @@ int fdr_policy_forward(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_la
   if (rc) return rc;
   if (!x || !out0 || (!k.discrete && !out1)) return set_error(FDR_ERR_INVALID, "NULL x/out");
   if (n_lanes == 0) return FDR_OK;
-  return launch_policy_forward(k, la, n_lanes, policy->bn_mean, policy->bn_var, x, out0, out1,
+  return launch_policy_forward(*C, k, la, n_lanes, policy->bn_mean, policy->bn_var, x, out0, out1,
                                (hipStream_t)stream);
 }
 
@@ -210,7 +213,8 @@ int fdr_diag_theta_prime(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_
   LanesArgs la;
   rc = lanes_args(lanes, n_lanes, k.n_params, &la);
   if (rc) return rc;
-  if (loader != FDR_LOADER_LANE && loader != FDR_LOADER_PAIR) return set_error(FDR_ERR_INVALID, "unknown loader");
+  if (loader != FDR_LOADER_LANE && loader != FDR_LOADER_PAIR && loader != FDR_LOADER_DYN)
+    return set_error(FDR_ERR_INVALID, "unknown loader");
   if (!out || !reads || !counted || !n2) return set_error(FDR_ERR_INVALID, "NULL output");
   if (n_lanes == 0) return FDR_OK;
   return launch_theta_prime(k, la, n_lanes, loader, policy->bn_mean, policy->bn_var, out, reads, counted, n2,

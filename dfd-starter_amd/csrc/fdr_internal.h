@@ -104,7 +104,7 @@ struct RolloutArgs {
   const float* u_inject;
 };
 
-int launch_policy_forward(const PolicyKey& k, const LanesArgs& lanes, int n_lanes,
+int launch_policy_forward(const Context& ctx, const PolicyKey& k, const LanesArgs& lanes, int n_lanes,
                           const float* bn_mean, const float* bn_var, const float* x, float* out0,
                           float* out1, hipStream_t stream);
 int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream);
@@ -139,10 +139,21 @@ inline bool physics_policy_ok(const PhysicsEnv& e, const PolicyKey& k) {
 int launch_rollout_env(const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream);
 // two lanes per wave; round_lanes: lanes of one resident round (more go out as consecutive launches)
 int launch_rollout_pair(const PolicyKey& k, const RolloutArgs& args, int round_lanes, hipStream_t stream);
-// fdr_diag_theta_prime: what MlpLane::load / MlpPair::load read through a RecordSrc (out / reads / counted [n_lanes, P])
+// fdr_diag_theta_prime: what MlpLane::load / MlpPair::load / DynLane::load read through a RecordSrc (out / reads /
+// counted [n_lanes, P])
 int launch_theta_prime(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, int loader, const float* bn_mean,
                        const float* bn_var, float* out, int32_t* reads, int32_t* counted, double* n2,
                        hipStream_t stream);
+// The runtime-shaped family (fdr_rollout_dyn.hip): n_in / n_act are kernel arguments.  It runs every shape within
+// dyn_shape_check's limits that is no compiled instance, and every synthetic-env rollout and policy forward of a
+// FDR_ROLLOUT_GENERIC context.  dyn_shape_check: FDR_OK, or FDR_ERR_UNSUPPORTED with the limit in the message.
+int dyn_shape_check(const PolicyKey& k);
+int launch_rollout_dyn(const PolicyKey& k, const RolloutArgs& args, hipStream_t stream);
+int launch_policy_forward_dyn(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, const float* bn_mean,
+                              const float* bn_var, const float* x, float* out0, float* out1, hipStream_t stream);
+int launch_theta_prime_dyn(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, const float* bn_mean,
+                           const float* bn_var, float* out, int32_t* reads, int32_t* counted, double* n2,
+                           hipStream_t stream);
 
 // fdr_rollout.hip: per-lane Welford obs statistics folded into the accumulated ones (fdr_obs_stats_merge)
 int launch_obs_stats_merge(const float* mean, const float* m2, const int32_t* count, int n, int d, float* acc_mean,

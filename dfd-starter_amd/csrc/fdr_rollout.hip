@@ -22,6 +22,8 @@
 //   fdr_rollout_wide.hip   rollout_kernel<WIDE>, synthetic env
 //   fdr_rollout_env.hip    rollout_kernel, trap / CartPole / Pendulum / Acrobot / MountainCar (both)
 //   fdr_rollout_pair.hip   rollout_pair_kernel                    (fdr_mlp_pair.h)
+//   fdr_rollout_dyn.hip    the runtime-shaped family: rollout, forward and loader read-back at any (n_in, n_act)
+//                          within Layout's limits                 (fdr_mlp_dyn.h)
 // fdr_mlp.h holds what they share: Layout, the compiled shapes (with_shape) and the feature bits.
 #include "fdr_mlp_lane.h"
 #include "fdr_mlp_pair.h"
@@ -64,9 +66,22 @@ __global__ __launch_bounds__(64 * kLanesPerBlock) void policy_forward_kernel(
   }
 }
 
-int launch_policy_forward(const PolicyKey& k, const LanesArgs& lanes, int n_lanes,
+// Is k's (n_in, n_act, discrete) one of the list's compiled shapes?
+template <class... S>
+static bool key_in(ShapeList<S...>, const PolicyKey& k) {
+  return ((k.n_in == S::NIN && k.n_act == S::NA && k.discrete == S::DISC) || ...);
+}
+// The runtime-shaped family (fdr_rollout_dyn.hip) takes every shape that is no compiled instance, and every shape
+// of a FDR_ROLLOUT_GENERIC context.
+static bool use_dyn_family(int rollout_impl, const PolicyKey& k) {
+  return rollout_impl == FDR_ROLLOUT_GENERIC || !(key_in(MlpShapes{}, k) || key_in(PhysicsShapes{}, k));
+}
+
+int launch_policy_forward(const Context& ctx, const PolicyKey& k, const LanesArgs& lanes, int n_lanes,
                           const float* bn_mean, const float* bn_var, const float* x, float* out0,
                           float* out1, hipStream_t stream) {
+  if (use_dyn_family(ctx.rollout_impl, k))
+    return launch_policy_forward_dyn(k, lanes, n_lanes, bn_mean, bn_var, x, out0, out1, stream);
   const dim3 grid((n_lanes + kLanesPerBlock - 1) / kLanesPerBlock), block(64 * kLanesPerBlock);
   return with_shape<true>(k, "no compiled policy_forward for this (kind, n_in, n_act)", [&](auto shape) {
     using S = decltype(shape);
@@ -97,6 +112,8 @@ static bool use_wide_kernel(const Context& ctx, int n_lanes) {
 
 int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream) {
   if (env_kind != FDR_ENV_SYNTH) return launch_rollout_env(k, env_kind, args, stream);
+  // (a PhysicsShapes shape under any other impl has no synthetic-env kernel: launch_rollout_lane refuses it)
+  if (use_dyn_family(ctx.rollout_impl, k)) return launch_rollout_dyn(k, args, stream);
   if (use_pair_kernel(ctx, args.n_lanes) && !args.os_mean && !args.u_inject)
     return launch_rollout_pair(k, args, pair_round_lanes(ctx), stream);
   if (use_wide_kernel(ctx, args.n_lanes) && !args.u_inject) return launch_rollout_wide(k, args, stream);
@@ -166,6 +183,9 @@ __global__ __launch_bounds__(64 * kPairWaves) void theta_prime_pair_kernel(Theta
 int launch_theta_prime(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, int loader, const float* bn_mean,
                        const float* bn_var, float* out, int32_t* reads, int32_t* counted, double* n2,
                        hipStream_t stream) {
+  // the dyn loader where it is asked for, and at every shape that has no compiled loader
+  if (loader == FDR_LOADER_DYN || use_dyn_family(FDR_ROLLOUT_AUTO, k))
+    return launch_theta_prime_dyn(k, lanes, n_lanes, bn_mean, bn_var, out, reads, counted, n2, stream);
   const ThetaPrimeArgs a{lanes, n_lanes, k.n_params, bn_mean, bn_var, out, reads, counted, n2};
   return with_shape<true>(k, "no compiled loader for this (kind, n_in, n_act)", [&](auto shape) {
     using S = decltype(shape);

@@ -15,8 +15,9 @@ FDR_ENV_SYNTH, FDR_ENV_TRAP, FDR_ENV_CARTPOLE, FDR_ENV_PENDULUM = 0, 1, 2, 3
 FDR_ENV_ACROBOT, FDR_ENV_MOUNTAINCAR, FDR_ENV_MOUNTAINCAR_CONT = 4, 5, 6
 FDR_DIST_L2, FDR_DIST_TVD, FDR_DIST_W2 = 0, 1, 2
 FDR_ROLLOUT_PAIR, FDR_ROLLOUT_SINGLE, FDR_ROLLOUT_AUTO, FDR_ROLLOUT_WIDE = 0, 1, 2, 3
+FDR_ROLLOUT_GENERIC = 4   # the runtime-shaped kernel family at every shape
 FDR_WEIGHT_ZSCORE, FDR_WEIGHT_CENTERED_RANK, FDR_WEIGHT_MOMENTS = 0, 1, 2
-FDR_LOADER_LANE, FDR_LOADER_PAIR = 0, 1   # include/fdr_diag.h
+FDR_LOADER_LANE, FDR_LOADER_PAIR, FDR_LOADER_DYN = 0, 1, 2   # include/fdr_diag.h
 
 EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy", "fdr_ctx_device",
            "fdr_perturb", "fdr_policy_forward", "fdr_rollout", "fdr_fd_weights",

@@ -48,9 +48,10 @@ class Context(object):
         self.handle = h
 
     def set_rollout_impl(self, impl):
-        """"pair" | "single" | "wide" | "auto" (FDR_ROLLOUT_*)."""
+        """"pair" | "single" | "wide" | "auto" | "generic" (FDR_ROLLOUT_*; "generic": the runtime-shaped kernels
+        for every synthetic-env rollout and policy forward of this context)."""
         code = {"pair": _lib.FDR_ROLLOUT_PAIR, "single": _lib.FDR_ROLLOUT_SINGLE, "auto": _lib.FDR_ROLLOUT_AUTO,
-                "wide": _lib.FDR_ROLLOUT_WIDE}[impl]
+                "wide": _lib.FDR_ROLLOUT_WIDE, "generic": _lib.FDR_ROLLOUT_GENERIC}[impl]
         check(lib.fdr_ctx_set_rollout_impl(self.handle, code), "fdr_ctx_set_rollout_impl")
 
     def set_replay_gemm(self, on):
@@ -150,7 +151,7 @@ def perturb(theta, table, idx, sign, sigma):
     return out
 
 
-def policy_forward(spec, lanes, n_lanes, x, bn_mean=None, bn_var=None):
+def policy_forward(spec, lanes, n_lanes, x, bn_mean=None, bn_var=None, ctx=None):
     """One observation per lane.  discrete -> probs [n, A]; mujoco -> (mean, std) [n, A]."""
     _check_dev(x, bn_mean, bn_var)
     x = x.to(torch.float32).contiguous()
@@ -158,23 +159,24 @@ def policy_forward(spec, lanes, n_lanes, x, bn_mean=None, bn_var=None):
     out0 = torch.empty((n_lanes, spec.n_act), dtype=torch.float32, device=dev)
     out1 = None if spec.kind == "discrete" else torch.empty_like(out0)
     pd = spec.desc(bn_mean, bn_var)
-    check(lib.fdr_policy_forward(_c(dev), ctypes.byref(pd), ctypes.byref(lanes), n_lanes, _p(x), _p(out0),
+    check(lib.fdr_policy_forward(_c(dev, ctx), ctypes.byref(pd), ctypes.byref(lanes), n_lanes, _p(x), _p(out0),
                                  _p(out1), _stream(dev)), "fdr_policy_forward")
     return out0 if out1 is None else (out0, out1)
 
 
-def theta_prime(spec, lanes, n_lanes, loader, bn_mean=None, bn_var=None, device=None):
+def theta_prime(spec, lanes, n_lanes, loader, bn_mean=None, bn_var=None, device=None, ctx=None):
     """Diagnostics (include/fdr_diag.h, fdr_diag_theta_prime): the weights one of the MLP rollouts' loaders forms,
-    read back.  loader "lane" | "pair".  -> (out f32, reads i32, counted i32) [n_lanes, P], n2 f64 [n_lanes]."""
+    read back.  loader "lane" | "pair" | "dyn" (the runtime-shaped kernels').  -> (out f32, reads i32, counted i32)
+    [n_lanes, P], n2 f64 [n_lanes]."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     _check_dev(bn_mean, bn_var)
-    code = {"lane": _lib.FDR_LOADER_LANE, "pair": _lib.FDR_LOADER_PAIR}[loader]
+    code = {"lane": _lib.FDR_LOADER_LANE, "pair": _lib.FDR_LOADER_PAIR, "dyn": _lib.FDR_LOADER_DYN}[loader]
     out = torch.full((n_lanes, spec.n_params), float("nan"), dtype=torch.float32, device=dev)
     reads = torch.zeros((n_lanes, spec.n_params), dtype=torch.int32, device=dev)
     counted = torch.zeros_like(reads)
     n2 = torch.full((n_lanes,), -1.0, dtype=torch.float64, device=dev)
     pd = spec.desc(bn_mean, bn_var)
-    check(lib.fdr_diag_theta_prime(_c(dev), ctypes.byref(pd), ctypes.byref(lanes), n_lanes, code, _p(out), _p(reads),
+    check(lib.fdr_diag_theta_prime(_c(dev, ctx), ctypes.byref(pd), ctypes.byref(lanes), n_lanes, code, _p(out), _p(reads),
                                    _p(counted), _p(n2), _stream(dev)), "fdr_diag_theta_prime")
     return out, reads, counted, n2
 

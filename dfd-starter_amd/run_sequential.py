@@ -105,7 +105,10 @@ class SequentialRunner(object):
                  omega_min_value=0, omega_max_value=1, omega_steps_to_min=25, omega_steps_to_max=75,
                  log_to_wandb=False, wandb_project="fd-starter", wandb_group=None, wandb_run_name=None,
                  noise_table_size=25_000_000, antithetic=False, episode_len=None, device=None, verbose=True,
-                 envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False):
+                 envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False, env_shape=None):
+        """env_shape = (obs_dim, act_dim, discrete): instead of the env_id mapping, a SyntheticEnv of that shape
+        (episode_len, default 1000) with the matching DiscretePolicy / MujocoPolicy -- any shape the engine's
+        runtime-shaped kernels take (obs_dim <= 64; act_dim <= 16 discrete, <= 8 continuous).  None: env_id."""
         if log_to_wandb:
             raise NotImplementedError("wandb logging is not part of the MI355X engine (no network)")
         self.verbose = verbose
@@ -120,8 +123,13 @@ class SequentialRunner(object):
         torch.manual_seed(random_seed)
         np.random.seed(random_seed)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.env = make_env(env_id, self.device, episode_len, envs_per_lane=envs_per_lane, fp16=fp16, policy=policy,
-                            physics=physics)
+        if env_shape is not None:
+            obs_dim, act_dim, discrete = env_shape
+            self.env = SyntheticEnv(obs_dim, act_dim, discrete, 1000 if episode_len is None else episode_len,
+                                    device=self.device)
+        else:
+            self.env = make_env(env_id, self.device, episode_len, envs_per_lane=envs_per_lane, fp16=fp16,
+                                policy=policy, physics=physics)
         self.frames = isinstance(self.env, FrameEnv)
         if isinstance(self.env, StackedFrameEnv):      # utils/init_helper.py:13-18
             self.policy = AtariPolicy(self.env.obs_shape, self.env.act_dim, seed=random_seed, device=self.device)

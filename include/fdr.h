@@ -29,7 +29,7 @@ extern "C" {
 
 #define FDR_OK 0
 #define FDR_ERR_INVALID 1     /* bad argument (null pointer, size, shape mismatch) */
-#define FDR_ERR_UNSUPPORTED 2 /* policy/env shape with no compiled kernel instance */
+#define FDR_ERR_UNSUPPORTED 2 /* policy/env shape no kernel runs (outside the limits under FDR_ROLLOUT_* below) */
 #define FDR_ERR_HIP 3         /* HIP runtime error (launch failure, no device) */
 #define FDR_ERR_WORKSPACE 4   /* caller's workspace too small */
 
@@ -161,12 +161,24 @@ int fdr_rollout(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_desc*
  *                       in registers, readlane input broadcast, per-action candidate next states
  *   FDR_ROLLOUT_AUTO    the pair kernel when n_lanes >= 16 x CUs (two pair waves per SIMD), wide when
  *                       n_lanes <= 8 x CUs (every lane in one pass at 2 waves per SIMD), else single
+ *   FDR_ROLLOUT_GENERIC the runtime-shaped family (added within fdr 0.5: one constant, no new export): one lane per
+ *                       wave with n_in / n_act as kernel arguments (rollout_dyn_kernel).  Every
+ *                       synthetic-env rollout and every fdr_policy_forward of the context takes it, the compiled
+ *                       shapes and the physics envs' shapes included (the trap and physics envs keep their kernels).
  * All compute the same episodes; sums are ordered differently (parity tolerances hold for each).
- * "pair" / "single" / "wide" are also the FDR_ROLLOUT environment variable's values. */
+ * "pair" / "single" / "wide" / "generic" are also the FDR_ROLLOUT environment variable's values.
+ *
+ * Policy shapes.  Six (n_in, n_act) are compiled instances of every kernel above -- discrete (2, 9), (4, 2), (8, 4);
+ * mujoco (17, 6), (11, 3), (8, 2) -- and the physics envs bring their own four.  Every other shape runs on the
+ * runtime-shaped family whatever the selection, in fdr_rollout*, fdr_policy_forward and fdr_diag_theta_prime alike:
+ *   1 <= n_in <= 64;  discrete: 1 <= n_act <= 16;  mujoco: 1 <= n_act <= 8 (a head of 2 n_act <= 16 outputs).
+ * Outside these limits: FDR_ERR_UNSUPPORTED, the limit named in fdr_last_error(), nothing launched.  A physics
+ * env's shape with the synthetic env stays FDR_ERR_UNSUPPORTED under every selection but FDR_ROLLOUT_GENERIC. */
 #define FDR_ROLLOUT_PAIR 0
 #define FDR_ROLLOUT_SINGLE 1
 #define FDR_ROLLOUT_AUTO 2
 #define FDR_ROLLOUT_WIDE 3
+#define FDR_ROLLOUT_GENERIC 4
 int fdr_rollout_set_impl(int32_t impl);
 
 /* Same as fdr_rollout, and also writes every visited raw observation (before normalisation) to

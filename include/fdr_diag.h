@@ -38,12 +38,15 @@ int fdr_impala_set_replay_gemm(int32_t on);
 /* Read-back of the perturbed weights theta' = fl32(theta +/- fl32(sigma * eps)) that the MLP rollouts' own loaders
  * form.  Runs only the lane's parameter source and one loader, under the thread mapping of the kernels that use it,
  * over a recording source: no environment, no policy step.  loader: FDR_LOADER_LANE = the one-lane-per-wave kernels'
- * (fdr_policy_forward, fdr_rollout single / wide, trap env), FDR_LOADER_PAIR = the pair kernel's.  DEVICE outputs,
+ * (fdr_policy_forward, fdr_rollout single / wide, trap env), FDR_LOADER_PAIR = the pair kernel's, FDR_LOADER_DYN =
+ * the runtime-shaped family's (FDR_ROLLOUT_GENERIC; any shape within its limits -- a shape with no compiled instance
+ * is read back through this loader whichever is named).  DEVICE outputs,
  * [n_lanes, n_params] each: out = the value the loader was given for element p; reads = how many loads asked for it;
  * counted = how many of those entered the lane's norm2 (reads and counted must be zero on entry: they are added to).
  * n2: DEVICE f64 [n_lanes], the norm2 the rollout would report (NaN for an out-of-range offset). */
 #define FDR_LOADER_LANE 0
 #define FDR_LOADER_PAIR 1
+#define FDR_LOADER_DYN 2
 int fdr_diag_theta_prime(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_lanes_desc* lanes, int32_t n_lanes,
                          int32_t loader, float* out, int32_t* reads, int32_t* counted, double* n2, fdr_stream stream);
 

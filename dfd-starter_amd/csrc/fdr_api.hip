@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -351,6 +352,50 @@ int fdr_fd_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, doubl
                            norm2_local, lanes_per_dir, sigma, coef, (hipStream_t)stream);
 }
 
+// The mixed objective's channels as the kernels take them: refusals first, then an inactive channel (coefficient 0)
+// is pointed at the first active one's array, so the kernels' clamped loads need no NULL test and read nothing of
+// the caller's inactive array.
+static int mix_channels(const double* rewards_all, const double* novelty_all, const double* entropy_all,
+                        double policy_reward, double policy_novelty, double policy_entropy, double coef_reward,
+                        double coef_novelty, double coef_entropy, MixChannels& mx) {
+  mx = MixChannels{{rewards_all, novelty_all, entropy_all},
+                   {policy_reward, policy_novelty, policy_entropy},
+                   {coef_reward, coef_novelty, coef_entropy}};
+  const double* first = nullptr;
+  for (int c = 0; c < 3; ++c) {
+    if (!std::isfinite(mx.a[c])) return set_error(FDR_ERR_INVALID, "a coefficient of the mixed objective is not finite");
+    if (mx.a[c] != 0.0 && !mx.v[c])
+      return set_error(FDR_ERR_INVALID, "an active channel's array is NULL (its coefficient is not 0)");
+    if (mx.a[c] != 0.0 && !first) first = mx.v[c];
+  }
+  if (!first) return set_error(FDR_ERR_INVALID, "all three coefficients of the mixed objective are 0");
+  for (int c = 0; c < 3; ++c)
+    if (mx.a[c] == 0.0) {
+      mx.v[c] = first;
+      mx.p[c] = 0.0;
+    }
+  return FDR_OK;
+}
+
+int fdr_fd_weights_mix(fdr_ctx* ctx, const double* rewards_all, const double* novelty_all, const double* entropy_all,
+                       int32_t n_all, double policy_reward, double policy_novelty, double policy_entropy,
+                       double coef_reward, double coef_novelty, double coef_entropy, int32_t lane_lo, int32_t n_local,
+                       const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                       double* coef, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (!sign_local || !norm2_local || !coef) return set_error(FDR_ERR_INVALID, "NULL pointer");
+  if (n_all <= 0 || lane_lo < 0 || n_local < 0 || lane_lo + n_local > n_all)
+    return set_error(FDR_ERR_INVALID, "bad lane range");
+  if (lanes_per_dir < 1 || n_local % lanes_per_dir != 0)
+    return set_error(FDR_ERR_INVALID, "n_local must be a multiple of lanes_per_dir");
+  MixChannels mx;
+  const int rc = mix_channels(rewards_all, novelty_all, entropy_all, policy_reward, policy_novelty, policy_entropy,
+                              coef_reward, coef_novelty, coef_entropy, mx);
+  if (rc) return rc;
+  return launch_fd_weights_mix(mx, n_all, lane_lo, n_local, sign_local, norm2_local, lanes_per_dir, sigma, coef,
+                               (hipStream_t)stream);
+}
+
 int64_t fdr_fd_grad_workspace_bytes(int32_t n_dirs, int64_t n_params) {
   return grad_workspace_bytes(n_dirs, n_params);
 }
@@ -403,7 +448,7 @@ int64_t fdr_fd_grad_fused_counter_bytes(int32_t n_dirs, int64_t n_params) {
 
 int64_t fdr_fd_grad_fused_out_len(int32_t mode, int64_t n_params, int32_t n_all) {
   if (n_params <= 0) return -1;
-  if (mode == FDR_WEIGHT_ZSCORE || mode == FDR_WEIGHT_CENTERED_RANK) return n_params;
+  if (mode == FDR_WEIGHT_ZSCORE || mode == FDR_WEIGHT_CENTERED_RANK || mode == FDR_WEIGHT_ZSCORE_MIX) return n_params;
   if (mode == FDR_WEIGHT_MOMENTS) return n_all > 0 ? 2 * n_params + 1 + n_all : -1;
   return -1;
 }
@@ -413,17 +458,22 @@ static int fd_grad_fused_impl(const float* table, int64_t table_size, const int6
                               int32_t lane_lo, const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir,
                               float sigma, int32_t mode, double* out, float* theta, double lr, double lr_scale,
                               float* hist, double* dsgd_out, void* workspace, int64_t workspace_bytes,
-                              fdr_stream stream) {
+                              fdr_stream stream, const MixChannels* mix = nullptr) {
   if (!table || !out || n_params <= 0 || table_size < n_params || n_dirs < 0)
     return set_error(FDR_ERR_INVALID, "bad arguments");
-  if (mode != FDR_WEIGHT_ZSCORE && mode != FDR_WEIGHT_CENTERED_RANK && mode != FDR_WEIGHT_MOMENTS)
+  if (mode == FDR_WEIGHT_ZSCORE_MIX && !mix)
+    return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_grad_fused_mix / fdr_fd_step_mix");
+  if (mode != FDR_WEIGHT_ZSCORE && mode != FDR_WEIGHT_CENTERED_RANK && mode != FDR_WEIGHT_MOMENTS &&
+      mode != FDR_WEIGHT_ZSCORE_MIX)
     return set_error(FDR_ERR_INVALID, "unknown weighting mode");
   if (lanes_per_dir < 1) return set_error(FDR_ERR_INVALID, "lanes_per_dir < 1");
   if (n_dirs == 0) return set_error(FDR_ERR_INVALID, "no directions (DSGD would divide by ||g|| = 0)");
   const int n_local = n_dirs * lanes_per_dir;
-  if (!idx_local || !rewards_all || !sign_local || !norm2_local) return set_error(FDR_ERR_INVALID, "NULL pointer");
+  if (!idx_local || (!rewards_all && !mix) || !sign_local || !norm2_local)
+    return set_error(FDR_ERR_INVALID, "NULL pointer");
   if (n_all <= 0 || lane_lo < 0 || lane_lo + n_local > n_all) return set_error(FDR_ERR_INVALID, "bad lane range");
   FusedCall c{};
+  if (mix) c.mix = *mix;
   c.fd.table = table;
   c.fd.max_idx = table_size - n_params;
   c.fd.idx = idx_local;
@@ -453,6 +503,8 @@ int fdr_fd_grad_fused(fdr_ctx* ctx, const float* table, int64_t table_size, cons
                       int32_t mode, double* out, int64_t out_len, void* workspace, int64_t workspace_bytes,
                       fdr_stream stream) {
   FDR_CTX(ctx, C);
+  if (mode == FDR_WEIGHT_ZSCORE_MIX)
+    return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_grad_fused_mix / fdr_fd_step_mix");
   const int64_t need = fdr_fd_grad_fused_out_len(mode, n_params, n_all);
   if (need > 0 && out_len < need) return set_error(FDR_ERR_INVALID, "out_len below fdr_fd_grad_fused_out_len");
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, lane_lo,
@@ -468,10 +520,50 @@ int fdr_fd_step(fdr_ctx* ctx, const float* table, int64_t table_size, const int6
   FDR_CTX(ctx, C);
   if (!theta || !g || !out) return set_error(FDR_ERR_INVALID, "NULL theta / g / out");
   if (mode == FDR_WEIGHT_MOMENTS) return set_error(FDR_ERR_INVALID, "fdr_fd_step takes z-score or centred-rank weights");
+  if (mode == FDR_WEIGHT_ZSCORE_MIX)
+    return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_grad_fused_mix / fdr_fd_step_mix");
   if (n_all != n_dirs * lanes_per_dir) return set_error(FDR_ERR_INVALID, "fdr_fd_step is single-process: n_all = n_local");
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, 0,
                             sign_local, norm2_local, lanes_per_dir, sigma, mode, g, theta, lr, lr_scale, theta_hist,
                             out, workspace, workspace_bytes, stream);
+}
+
+int fdr_fd_grad_fused_mix(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local,
+                          int32_t n_dirs, int64_t n_params, const double* rewards_all, const double* novelty_all,
+                          const double* entropy_all, int32_t n_all, double policy_reward, double policy_novelty,
+                          double policy_entropy, double coef_reward, double coef_novelty, double coef_entropy,
+                          int32_t lane_lo, const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir,
+                          float sigma, double* out, int64_t out_len, void* workspace, int64_t workspace_bytes,
+                          fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  MixChannels mx;
+  const int rc = mix_channels(rewards_all, novelty_all, entropy_all, policy_reward, policy_novelty, policy_entropy,
+                              coef_reward, coef_novelty, coef_entropy, mx);
+  if (rc) return rc;
+  if (n_params > 0 && out_len < n_params) return set_error(FDR_ERR_INVALID, "out_len below fdr_fd_grad_fused_out_len");
+  return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, mx.v[0], n_all, mx.p[0], lane_lo,
+                            sign_local, norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_ZSCORE_MIX, out, nullptr, 0.0,
+                            0.0, nullptr, nullptr, workspace, workspace_bytes, stream, &mx);
+}
+
+int fdr_fd_step_mix(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                    int64_t n_params, const double* rewards_all, const double* novelty_all, const double* entropy_all,
+                    int32_t n_all, double policy_reward, double policy_novelty, double policy_entropy,
+                    double coef_reward, double coef_novelty, double coef_entropy, const int8_t* sign_local,
+                    const double* norm2_local, int32_t lanes_per_dir, float sigma, float* theta, double lr,
+                    double lr_scale, double* g, float* theta_hist, double* out, void* workspace,
+                    int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (!theta || !g || !out) return set_error(FDR_ERR_INVALID, "NULL theta / g / out");
+  MixChannels mx;
+  const int rc = mix_channels(rewards_all, novelty_all, entropy_all, policy_reward, policy_novelty, policy_entropy,
+                              coef_reward, coef_novelty, coef_entropy, mx);
+  if (rc) return rc;
+  if (n_all != n_dirs * lanes_per_dir)
+    return set_error(FDR_ERR_INVALID, "fdr_fd_step_mix is single-process: n_all = n_local");
+  return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, mx.v[0], n_all, mx.p[0], 0, sign_local,
+                            norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_ZSCORE_MIX, g, theta, lr, lr_scale,
+                            theta_hist, out, workspace, workspace_bytes, stream, &mx);
 }
 
 int fdr_rank_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, int32_t lane_lo, int32_t n_local,

@@ -13,6 +13,17 @@ int launch_perturb(const float* theta, int64_t P, const float* table, int64_t ta
 int launch_fd_weights(const double* r_all, int n_all, double pr, int lo, int n_local,
                       const int8_t* sign, const double* n2, int lpd, float sigma, double* coef,
                       hipStream_t stream);
+// The mixed objective's channels (reward, novelty, entropy), by value to kernels: w_i = sum over the channels with
+// a != 0, in this order, of a_c z_c[i], z_c the z-score of v_c - p_c over all lanes (input unchanged when its std is
+// 0).  A channel with a == 0 is inactive: the C boundary points its v at an active channel's array (so every load
+// stays branch-free and in bounds) and the kernels add no term for it.
+struct MixChannels {
+  const double* v[3];  // [n_all] each
+  double p[3];         // the policy's own value
+  double a[3];         // 1 - omega, omega, ent_coef
+};
+int launch_fd_weights_mix(const MixChannels& mx, int n_all, int lo, int n_local, const int8_t* sign, const double* n2,
+                          int lpd, float sigma, double* coef, hipStream_t stream);
 
 // The tiling of a noise-weighted gradient: 256-column blocks x row chunks, one f64 partial slab per chunk.  The
 // staged pair (grad_plan) and the fused kernel (fused_plan) choose rows_per_chunk by formulas of their own; each
@@ -81,9 +92,16 @@ struct FdArgs {
   double* out;           // g [P]; MOMENTS: [A | B | n_local | r' slots [n_all]]
   double* gsq;           // [col_blocks] sum fl32(-g)^2 per column block (fdr_fd_step), or NULL
 };
+// fd_grad_fused_mix_kernel's argument: FdArgs as it is (the existing instances' kernarg layout does not move) and
+// the channels; fd.r_all / fd.pr are not read, the reward channel is mix.v[0] / mix.p[0].
+struct FdMixArgs {
+  FdArgs fd;
+  MixChannels mix;
+};
 struct FusedCall {
   FdArgs fd;             // table .. sigma and out
   int mode;              // FDR_WEIGHT_*
+  MixChannels mix;       // FDR_WEIGHT_ZSCORE_MIX only
   // fdr_fd_step: DSGD in the same call (theta NULL: the gradient only)
   float* theta;
   double lr, lr_scale;

@@ -94,6 +94,60 @@ int launch_fd_weights(const double* r_all, int n_all, double pr, int lo, int n_l
   return check_launch("fd_weights_kernel");
 }
 
+// The mixed objective's staged weighting (fdr_fd_weights_mix; the delayed-return route): fd_weights_kernel with a
+// z-score per active channel (MixChannels), each over the same per-thread order and workgroup tree; an inactive
+// channel's array is not read.  With coefficients (1, 0, 0) the coefficients are fd_weights_kernel's bits.
+__global__ __launch_bounds__(1024) void fd_weights_mix_kernel(MixChannels mx, int n_all, int lo, int n_local,
+                                                               const int8_t* __restrict__ sign,
+                                                               const double* __restrict__ n2, int lpd, float sigma,
+                                                               double* __restrict__ coef) {
+  __shared__ double red[16];
+  double mean[3] = {0.0, 0.0, 0.0}, sd[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (mx.a[c] == 0.0) continue;  // uniform
+    const double* __restrict__ v = mx.v[c];
+    const double p = mx.p[c];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_all; i += blockDim.x) s += v[i] - p;
+    mean[c] = block_sum_1024(s, red) / (double)n_all;
+    double q = 0.0;
+    for (int i = threadIdx.x; i < n_all; i += blockDim.x) {
+      const double d = (v[i] - p) - mean[c];
+      q += d * d;
+    }
+    sd[c] = sqrt(block_sum_1024(q, red) / (double)n_all);
+  }
+  const int n_dirs = n_local / lpd;
+  for (int d = threadIdx.x; d < n_dirs; d += blockDim.x) {
+    double cf = 0.0;
+    for (int k = 0; k < lpd; ++k) {
+      const int i = d * lpd + k;
+      const int sg = sign[i];
+      if (sg == 0) continue;
+      double w = 0.0;
+      bool any = false;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if (mx.a[c] == 0.0) continue;
+        const double x = mx.v[c][lo + i] - mx.p[c];
+        const double t = mx.a[c] * (sd[c] == 0.0 ? x : (x - mean[c]) / sd[c]);  // utils/math_helpers.py:127-134
+        w = any ? w + t : t;
+        any = true;
+      }
+      cf += w * (double)sg * (double)sigma / n2[i];
+    }
+    coef[d] = cf;
+  }
+}
+
+int launch_fd_weights_mix(const MixChannels& mx, int n_all, int lo, int n_local, const int8_t* sign, const double* n2,
+                          int lpd, float sigma, double* coef, hipStream_t stream) {
+  hipLaunchKernelGGL(fd_weights_mix_kernel, dim3(1), dim3(1024), 0, stream, mx, n_all, lo, n_local, sign, n2, lpd,
+                     sigma, coef);
+  return check_launch("fd_weights_mix_kernel");
+}
+
 // ------------------------------------------------------------------------------------------
 // Noise-weighted gradient: g[p] = sum_d coef[d] * table[idx[d] + p]
 // ------------------------------------------------------------------------------------------

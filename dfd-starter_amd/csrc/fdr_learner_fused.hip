@@ -1,5 +1,6 @@
 // fdr_learner_fused.hip -- the fused learner step: weighting, noise-weighted gradient and chunk combine in one launch
-// (fd_grad_fused_kernel), the DSGD that can follow it in the same call (dsgd_apply_cb_kernel), centred-rank weights.
+// (fd_grad_fused_kernel; fd_grad_fused_mix_kernel for the reward / novelty / entropy objective), the DSGD that can
+// follow it in the same call (dsgd_apply_cb_kernel), centred-rank weights.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -283,6 +284,243 @@ __global__ __launch_bounds__(256) void fd_grad_fused_kernel(FdArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The mixed objective (fdr_fd_grad_fused_mix / fdr_fd_step_mix, FDR_WEIGHT_ZSCORE_MIX): the z-score instance with
+// three channels, w_i = a_r z_r[i] + a_n z_n[i] + a_e z_e[i] over the active ones (MixChannels, fdr_learner.h).  A
+// kernel of its own, so that fd_grad_fused_kernel's three instances and FdArgs stay what they are, instruction for
+// instruction; the tiling, the load order (statistics inputs, then the chunk's first 64 rows), the NaN coefficient,
+// the chunk combine and the sum fl32(-g)^2 partials are that kernel's, restated.
+//
+// Registers: the z-score instance holds 16 x values per thread (32 VGPRs) beside v[64] at 153 VGPRs, 3 waves per
+// SIMD -- what keeps config 3's 768 workgroups resident at once.  Three channels at 16 would take 96: kMixR = 4 per
+// channel (24 VGPRs; n_all <= 1024 entirely in registers) and the per-lane inputs of directions of up to kMixLpd = 2
+// lanes (antithetic pairs) stay under that line; lanes beyond either are read again from memory (L2-hot: every
+// workgroup reads the same 3 n_all doubles), kMixTail per channel in flight, after the table rows: 152 VGPRs, no
+// scratch, 3 waves per SIMD.  (kMixTail = 6: 166 VGPRs and no faster at config 3, 27.9 against 27.4 us -- the three
+// statistics chains cost what the r11 probe put on one, ~2.2 us each, not the tail's round trips.)  Per thread the
+// sums run over i = tid, tid + 256, .. in this order whatever kMixR is, and the workgroup tree is block_sum_256's:
+// with coefficients (1, 0, 0) the statistics, the weights and g are the z-score instance's bits.
+// ------------------------------------------------------------------------------------------
+constexpr int kMixR = 4;     // x values per channel held in registers
+constexpr int kMixLpd = 2;   // lanes of a thread's first direction whose inputs are held in registers
+constexpr int kMixTail = 4;  // lanes per channel in flight in the tail loops
+
+// a workgroup-uniform f64 into scalar registers (same bits)
+__device__ __forceinline__ double uniform_f64(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// block_sum_256 of three values at once: the same wave_sum and the same slot order per value, one barrier pair
+__device__ __forceinline__ void block_sum3_256(double (&s)[3], double (*red3)[4]) {
+  const int w = threadIdx.x >> 6, j = threadIdx.x & 63;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double t = wave_sum(s[c]);
+    if (j == 0) red3[c][w] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < 3; ++c) s[c] = uniform_f64(red3[c][0] + red3[c][1] + red3[c][2] + red3[c][3]);
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void fd_grad_fused_mix_kernel(FdMixArgs m) {
+  const FdArgs& a = m.fd;
+  __shared__ double cA[kFusedMaxRows];
+  __shared__ double red[4];
+  __shared__ double red3[3][4];
+  __shared__ int s_flag;
+  const int tid = threadIdx.x;
+  const int chunk = blockIdx.y, cb = blockIdx.x;
+  const int d0 = chunk * a.rows_per_chunk, d1 = min(a.n_dirs, d0 + a.rows_per_chunk);
+  const int64_t P = a.P;
+  const int64_t col = (int64_t)cb * 256 + tid;
+  const bool ok = col < P;
+  const int64_t cc = ok ? col : 0;
+  const bool act0 = m.mix.a[0] != 0.0, act1 = m.mix.a[1] != 0.0, act2 = m.mix.a[2] != 0.0;
+  auto row_off = [&](int d) {
+    const int64_t off = a.idx[(int64_t)d * a.lpd];
+    return (off < 0 || off > a.max_idx) ? (int64_t)-1 : off;
+  };
+  float v[kFusedRows];
+  // as fd_grad_fused_kernel: one vector load of the pass's 64 offsets (clamped into the chunk, an invalid offset
+  // reads row 0 under a NaN coefficient), each row's taken by v_readlane
+  auto row_offsets = [&](int r0) {
+    int64_t off = a.idx[(int64_t)min(r0 + (tid & 63), d1 - 1) * a.lpd];
+    return (off < 0 || off > a.max_idx) ? (int64_t)0 : off;
+  };
+  auto load_pass = [&](int r0, int64_t offl) {
+    const unsigned lo = (unsigned)offl, hi = (unsigned)((uint64_t)offl >> 32);
+#pragma unroll
+    for (int r = 0; r < kFusedRows; ++r) {
+      const int64_t o = (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readlane((int)hi, r) << 32) |
+                                  (unsigned)__builtin_amdgcn_readlane((int)lo, r));
+      const float x = a.table[o + cc];
+      v[r] = r0 + r < d1 ? x : 0.f;
+    }
+  };
+  const int64_t off0 = row_offsets(d0);
+  // the statistics' inputs before the table rows, branch-free with clamped indices (fd_grad_fused_kernel says why)
+  const int dmine = d0 + tid;
+  double xin[3][kMixLpd], vin[kMixLpd];
+  {
+    const int nloc = max(1, (d1 - d0) * a.lpd);
+    int sg[kMixLpd];
+    double n2v[kMixLpd], xv[3][kMixLpd];
+#pragma unroll
+    for (int k = 0; k < kMixLpd; ++k) {
+      const int i = d0 * a.lpd + min((dmine - d0) * a.lpd + k, nloc - 1);
+      sg[k] = a.sign[i];
+      n2v[k] = a.n2[i];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) xv[c][k] = m.mix.v[c][a.lo + i];
+    }
+#pragma unroll
+    for (int k = 0; k < kMixLpd; ++k) {
+      const double q = (double)sg[k] * (double)a.sigma / n2v[k];
+      const bool use = dmine < d1 && k < a.lpd && sg[k] != 0;
+      vin[k] = use ? q : 0.0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) xin[c][k] = use ? xv[c][k] - m.mix.p[c] : 0.0;
+    }
+  }
+  double xr[3][kMixR];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < kMixR; ++k) xr[c][k] = m.mix.v[c][min(tid + 256 * k, a.n_all - 1)];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < kMixR; ++k) xr[c][k] = tid + 256 * k < a.n_all ? xr[c][k] - m.mix.p[c] : 0.0;
+  load_pass(d0, off0);  // the table rows: in flight through the statistics and the coefficients
+  double mean[3], sd[3];
+  {
+    double s[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < kMixR; ++k)
+        if (tid + 256 * k < a.n_all) s[c] += xr[c][k];
+    for (int b = 256 * kMixR; b < a.n_all; b += 256 * kMixTail) {  // the tail: kMixTail x 3 loads in flight
+      double t[3][kMixTail];
+#pragma unroll
+      for (int e = 0; e < kMixTail; ++e)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[c][e] = m.mix.v[c][min(b + 256 * e + tid, a.n_all - 1)];
+#pragma unroll
+      for (int e = 0; e < kMixTail; ++e)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          if (b + 256 * e + tid < a.n_all) s[c] += t[c][e] - m.mix.p[c];
+    }
+    block_sum3_256(s, red3);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mean[c] = s[c] / (double)a.n_all;
+    double q[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < kMixR; ++k)
+        if (tid + 256 * k < a.n_all) {
+          const double d = xr[c][k] - mean[c];
+          q[c] += d * d;
+        }
+    for (int b = 256 * kMixR; b < a.n_all; b += 256 * kMixTail) {
+      double t[3][kMixTail];
+#pragma unroll
+      for (int e = 0; e < kMixTail; ++e)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[c][e] = m.mix.v[c][min(b + 256 * e + tid, a.n_all - 1)];
+#pragma unroll
+      for (int e = 0; e < kMixTail; ++e)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          if (b + 256 * e + tid < a.n_all) {
+            const double d = (t[c][e] - m.mix.p[c]) - mean[c];
+            q[c] += d * d;
+          }
+    }
+    block_sum3_256(q, red3);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sd[c] = sqrt(q[c] / (double)a.n_all);
+  }
+  auto zs = [&](int c, double x) { return sd[c] == 0.0 ? x : (x - mean[c]) / sd[c]; };  // math_helpers.py:127-134
+  auto weight = [&](double x0, double x1, double x2) {  // the active channels' terms, in channel order
+    double w = 0.0;
+    if (act0) w = m.mix.a[0] * zs(0, x0);
+    if (act1) {
+      const double t = m.mix.a[1] * zs(1, x1);
+      w = act0 ? w + t : t;
+    }
+    if (act2) {
+      const double t = m.mix.a[2] * zs(2, x2);
+      w = (act0 || act1) ? w + t : t;
+    }
+    return w;
+  };
+  if (dmine < d1 && a.lpd <= kMixLpd) {
+    double c = 0.0;
+#pragma unroll
+    for (int k = 0; k < kMixLpd; ++k)
+      if (k < a.lpd && vin[k] != 0.0) c += weight(xin[0][k], xin[1][k], xin[2][k]) * vin[k];
+    if (row_off(dmine) < 0) c = __builtin_nan("");
+    cA[dmine - d0] = c;
+  }
+  for (int d = d0 + tid + (a.lpd <= kMixLpd ? 256 : 0); d < d1; d += 256) {  // further directions of this thread
+    double c = 0.0;
+    for (int k = 0; k < a.lpd; ++k) {
+      const int i = d * a.lpd + k;
+      const int sg = a.sign[i];
+      if (sg == 0) continue;
+      const double vi = (double)sg * (double)a.sigma / a.n2[i];
+      c += weight(m.mix.v[0][a.lo + i] - m.mix.p[0], m.mix.v[1][a.lo + i] - m.mix.p[1],
+                  m.mix.v[2][a.lo + i] - m.mix.p[2]) * vi;
+    }
+    if (row_off(d) < 0) c = __builtin_nan("");
+    cA[d - d0] = c;
+  }
+  __syncthreads();
+
+  double acc0 = 0.0, acc1 = 0.0;
+  for (int r0 = d0; r0 < d1; r0 += kFusedRows) {
+    if (r0 != d0) load_pass(r0, row_offsets(r0));
+#pragma unroll
+    for (int r = 0; r < kFusedRows; r += 2) {
+      if (r0 + r < d1) acc0 = fma(cA[r0 + r - d0], (double)v[r], acc0);
+      if (r0 + r + 1 < d1) acc1 = fma(cA[r0 + r + 1 - d0], (double)v[r + 1], acc1);
+    }
+  }
+  const double ga = acc0 + acc1;
+
+  bool owner = true;  // this workgroup holds the final g of its column block
+  double gfin = ga;
+  if (a.n_chunks == 1) {
+    if (ok) store_wt(a.out + col, ga);
+  } else {
+    if (ok) store_wt(a.partial + (int64_t)chunk * P + col, ga);
+    publish_and_ticket(a.cnt + cb, (unsigned)a.n_chunks, &s_flag);
+    owner = s_flag != 0;
+    if (owner) {
+      double sa = 0.0;
+      if (ok) {
+        sa = sum_slabs(a.partial + col, P, a.n_chunks);
+        store_wt(a.out + col, sa);  // read by the DSGD workgroup of fdr_fd_step_mix
+      }
+      gfin = sa;
+      if (tid == 0) __hip_atomic_store(a.cnt + cb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  if (a.gsq && owner) {  // fdr_fd_step_mix: this column block's sum fl32(-g)^2 for the DSGD launch
+    const float gr = ok ? (float)(-gfin) : 0.f;
+    const double part = block_sum_256((double)gr * (double)gr, red);
+    if (tid == 0) a.gsq[cb] = part;
+  }
+}
+
 // DSGD after fd_grad_fused (fdr_fd_step): one 256-column block per workgroup.  Every workgroup forms
 // ||fl32(-g)|| from the per-column-block partials in the same order, updates its columns
 // (dynamic_sgd.py:19-39), writes theta_new to the history slot (the learner's policy_history,
@@ -420,6 +658,9 @@ int launch_fd_grad_fused(const FusedCall& c, void* ws, int64_t ws_bytes, hipStre
     case FDR_WEIGHT_MOMENTS:
       if (c.theta) return set_error(FDR_ERR_INVALID, "the moments form is reduced across ranks before DSGD");
       hipLaunchKernelGGL(fd_grad_fused_kernel<FDR_WEIGHT_MOMENTS>, grid, dim3(256), 0, stream, a);
+      break;
+    case FDR_WEIGHT_ZSCORE_MIX:
+      hipLaunchKernelGGL(fd_grad_fused_mix_kernel, grid, dim3(256), 0, stream, FdMixArgs{a, c.mix});
       break;
     default:
       return set_error(FDR_ERR_INVALID, "unknown weighting mode");

@@ -17,6 +17,7 @@ FDR_DIST_L2, FDR_DIST_TVD, FDR_DIST_W2 = 0, 1, 2
 FDR_ROLLOUT_PAIR, FDR_ROLLOUT_SINGLE, FDR_ROLLOUT_AUTO, FDR_ROLLOUT_WIDE = 0, 1, 2, 3
 FDR_ROLLOUT_GENERIC = 4   # the runtime-shaped kernel family at every shape
 FDR_WEIGHT_ZSCORE, FDR_WEIGHT_CENTERED_RANK, FDR_WEIGHT_MOMENTS = 0, 1, 2
+FDR_WEIGHT_ZSCORE_MIX = 3   # reward / novelty / entropy: fdr_fd_grad_fused_mix, fdr_fd_step_mix
 FDR_LOADER_LANE, FDR_LOADER_PAIR, FDR_LOADER_DYN = 0, 1, 2   # include/fdr_diag.h
 
 EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy", "fdr_ctx_device",
@@ -37,7 +38,7 @@ EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy",
            "fdr_ctx_impala_profile_read", "fdr_ctx_impala_debug_clock", "fdr_noise_draw_indices",
            "fdr_impala_bn_refresh_workspace_bytes", "fdr_impala_bn_refresh", "fdr_atari_strategies_workspace_bytes",
            "fdr_atari_strategies", "fdr_atari_bn_refresh_workspace_bytes", "fdr_atari_bn_refresh",
-           "fdr_diag_theta_prime")
+           "fdr_diag_theta_prime", "fdr_fd_grad_fused_mix", "fdr_fd_step_mix", "fdr_fd_weights_mix")
 
 
 class FDRError(RuntimeError):
@@ -142,6 +143,12 @@ def _load():
         "fdr_rank_weights": (ctypes.c_int, [P, P, I32, I32, I32, P, P]),
         "fdr_fd_step": (ctypes.c_int, [P, P, I64, P, I32, I64, P, I32, F64, P, P, I32, F32, I32, P, F64, F64, P, P, P,
                                        P, I64, P]),
+        "fdr_fd_grad_fused_mix": (ctypes.c_int, [P, P, I64, P, I32, I64, P, P, P, I32, F64, F64, F64, F64, F64, F64, I32,
+                                                 P, P, I32, F32, P, I64, P, I64, P]),
+        "fdr_fd_step_mix": (ctypes.c_int, [P, P, I64, P, I32, I64, P, P, P, I32, F64, F64, F64, F64, F64, F64, P, P, I32,
+                                           F32, P, F64, F64, P, P, P, P, I64, P]),
+        "fdr_fd_weights_mix": (ctypes.c_int, [P, P, P, P, I32, F64, F64, F64, F64, F64, F64, I32, I32, P, P, I32, F32, P,
+                                              P]),
         "fdr_dsgd_step_ex": (ctypes.c_int, [P, P, P, I32, I64, F64, F64, P, P, P, I64, P]),
         "fdr_dsgd_step": (ctypes.c_int, [P, P, P, I64, F64, F64, P, P, I64, P]),
         "fdr_atari_env_frames": (ctypes.c_int, [ctypes.c_uint64, I64, I32, I32, P, P]),

@@ -296,7 +296,75 @@ def _fused_workspace(mode, n_dirs, lanes_per_dir, n_params, device):
 
 
 WEIGHT_MODES = {"zscore": _lib.FDR_WEIGHT_ZSCORE, "centred_rank": _lib.FDR_WEIGHT_CENTERED_RANK,
-                "moments": _lib.FDR_WEIGHT_MOMENTS}
+                "moments": _lib.FDR_WEIGHT_MOMENTS, "zscore_mix": _lib.FDR_WEIGHT_ZSCORE_MIX}
+
+
+def _mix_channels(channels, policy_values, coefs):
+    """(reward, novelty, entropy) device f64 arrays (None: not given -- legal where the coefficient is 0), the
+    policy's own three values and the three coefficients -> (arrays, device, n_all, 6 floats)."""
+    channels = tuple(channels)
+    if len(channels) != 3 or len(policy_values) != 3 or len(coefs) != 3:
+        raise ValueError("the mixed objective takes three channels: reward, novelty, entropy")
+    given = [c for c in channels if c is not None]
+    if not given:
+        raise ValueError("the mixed objective needs at least one channel array")
+    for c in given:
+        if c.dtype != torch.float64 or c.numel() != given[0].numel() or not c.is_contiguous():
+            raise ValueError("channel arrays are contiguous f64 of one length")
+    _check_dev(*given)
+    vals = [float(0.0 if v is None else v) for v in policy_values] + [float(a) for a in coefs]
+    return channels, given[0].device, given[0].numel(), vals
+
+
+def fd_grad_fused_mix(table, idx_local, channels, policy_values, coefs, lane_lo, sign_local, norm2_local, lanes_per_dir,
+                      sigma, n_params, out=None):
+    """fd_grad_fused with the mixed weights (fdr_fd_grad_fused_mix): channels = (rewards_all, novelty_all,
+    entropy_all) over all lanes, policy_values and coefs in the same order; a channel whose coefficient is 0 may be
+    None and is never read.  -> g f64 [P]."""
+    channels, dev, n_all, vals = _mix_channels(channels, policy_values, coefs)
+    _check_dev(table, idx_local, sign_local, norm2_local, channels[0], channels[1], channels[2])
+    n_dirs = idx_local.numel() // int(lanes_per_dir)
+    if out is None:
+        out = torch.empty(n_params, dtype=torch.float64, device=dev)
+    ws = _fused_workspace(_lib.FDR_WEIGHT_ZSCORE_MIX, n_dirs, lanes_per_dir, n_params, dev)
+    check(lib.fdr_fd_grad_fused_mix(_c(dev), _p(table), table.numel(), _p(idx_local), n_dirs, n_params, _p(channels[0]),
+                                    _p(channels[1]), _p(channels[2]), n_all, *vals, int(lane_lo), _p(sign_local),
+                                    _p(norm2_local), int(lanes_per_dir), float(sigma), _p(out), out.numel(), _p(ws),
+                                    ws.numel(), _stream(dev)), "fdr_fd_grad_fused_mix")
+    return out
+
+
+def fd_step_mix(table, idx_local, channels, policy_values, coefs, sign_local, norm2_local, lanes_per_dir, sigma, theta,
+                lr, lr_scale, g=None, out=None, theta_hist=None):
+    """fd_step with the mixed weights (fdr_fd_step_mix); channels / policy_values / coefs as fd_grad_fused_mix.
+    Returns device f64[2] = (||d theta||, ||grad||)."""
+    channels, dev, n_all, vals = _mix_channels(channels, policy_values, coefs)
+    _check_dev(table, idx_local, sign_local, norm2_local, theta, g, theta_hist, channels[0], channels[1], channels[2])
+    P = theta.numel()
+    n_dirs = idx_local.numel() // int(lanes_per_dir)
+    if g is None:
+        g = torch.empty(P, dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = _fused_workspace(_lib.FDR_WEIGHT_ZSCORE_MIX, n_dirs, lanes_per_dir, P, dev)
+    check(lib.fdr_fd_step_mix(_c(dev), _p(table), table.numel(), _p(idx_local), n_dirs, P, _p(channels[0]),
+                              _p(channels[1]), _p(channels[2]), n_all, *vals, _p(sign_local), _p(norm2_local),
+                              int(lanes_per_dir), float(sigma), _p(theta), float(lr), float(lr_scale), _p(g),
+                              _p(theta_hist), _p(out), _p(ws), ws.numel(), _stream(dev)), "fdr_fd_step_mix")
+    return out
+
+
+def fd_weights_mix(channels, policy_values, coefs, lane_lo, sign_local, norm2_local, lanes_per_dir, sigma, coef=None):
+    """fd_weights with the mixed weights (fdr_fd_weights_mix) -> coef f64 [n_dirs]."""
+    channels, dev, n_all, vals = _mix_channels(channels, policy_values, coefs)
+    _check_dev(sign_local, norm2_local, channels[0], channels[1], channels[2])
+    n_local = sign_local.numel()
+    if coef is None:
+        coef = torch.empty(n_local // int(lanes_per_dir), dtype=torch.float64, device=dev)
+    check(lib.fdr_fd_weights_mix(_c(dev), _p(channels[0]), _p(channels[1]), _p(channels[2]), n_all, *vals, int(lane_lo),
+                                 n_local, _p(sign_local), _p(norm2_local), int(lanes_per_dir), float(sigma), _p(coef),
+                                 _stream(dev)), "fdr_fd_weights_mix")
+    return coef
 
 
 def fd_grad_fused(table, idx_local, rewards_all, policy_reward, lane_lo, sign_local, norm2_local, lanes_per_dir, sigma,

@@ -17,6 +17,13 @@ instead.
 ``weighting="centred_rank"`` (build extension named by the north star; the reference's weighting is the
 z-score) ranks all returns, so it keeps the all-gather of the per-lane returns + the all-reduce of g.
 
+``objective="mixed"`` (build extension; the reference carries the combination at finite_differences.py:40-48, switched
+off) weights lane i by (1 - omega) z(r_i - r_pol) + omega z(nov_i - nov_pol) + ent_coef z(ent_i - ent_pol), every
+channel standardised over all lanes, with omega read from ``self.omega`` at the step: fdr_fd_step_mix /
+fdr_fd_grad_fused_mix in place of the two calls above, fdr_fd_weights_mix on the delayed-return route.  Sharded it
+takes the gather form (one all-gather of the three channels stacked, one all-reduce of g).  ``objective="reward"``,
+the default, is the reference's step; "mixed" with omega = 0 and ent_coef = 0 equals it bit for bit.
+
 Returns carry a current epoch in the synchronous engine; returns from an older epoch (the
 reference's async server mode) add the parameter drift theta_epoch - theta_now to lambda
 (finite_differences.py:66-92) -- fdr_fd_lambda_norms / fdr_fd_grad_lambda, single-process or sharded
@@ -38,10 +45,18 @@ FUSED_STEP_MAX_P = 1 << 16   # fdr_fd_step fuses DSGD into the gradient launch u
 
 class FiniteDifferences(object):
     def __init__(self, policy, gradient_optimizer, omega, noise_source, noise_std=0.1, batch_size=100,
-                 ent_coef=0.0, max_delayed_return=10, process_group=None, weighting="zscore", one_collective=True):
+                 ent_coef=0.0, max_delayed_return=10, process_group=None, weighting="zscore", one_collective=True,
+                 objective="reward"):
         if weighting not in ("zscore", "centred_rank"):
             raise ValueError("weighting must be 'zscore' (the reference) or 'centred_rank'")
+        if objective not in ("reward", "mixed"):
+            raise ValueError("objective must be 'reward' (the reference's step) or 'mixed'")
+        if objective == "mixed" and weighting != "zscore":
+            raise ValueError("objective='mixed' standardises each channel: weighting='centred_rank' is not built for it")
         self.weighting = weighting
+        self.objective = objective
+        self.last_mix = None    # objective="mixed": the (reward, novelty, entropy) coefficients of the latest step
+        self._policy_values = (0.0, 0.0, 0.0)   # ... and the policy's own reward, novelty, entropy it subtracted
         self.one_collective = one_collective
         self.max_delayed_return = max_delayed_return
         self.ent_coef = ent_coef
@@ -84,6 +99,8 @@ class FiniteDifferences(object):
         """Same as step() but leaves (||d theta||, ||grad||) on the device: no host sync."""
         if policy_reward is None:
             policy_reward = 0
+        if self.objective == "mixed":
+            self._policy_values = (float(policy_reward), float(policy_novelty or 0), float(policy_entropy or 0))
         if isinstance(batch, FDBatch):
             return self._step_batch(batch, float(policy_reward))
         return self._step_returns(list(batch), float(policy_reward))
@@ -98,10 +115,71 @@ class FiniteDifferences(object):
             raise ValueError("a host noise source's FDBatch carries its noise rows (Worker.evaluate sets noise_table)")
         return self.noise_source.device_table(self.policy.flat.device)
 
+    def _mix_coefs(self):
+        """(1 - omega, omega, ent_coef) at this step (NSRA-ES; the reference's finite_differences.py:40-48)."""
+        w = float(self.omega.omega)
+        self.last_mix = (1.0 - w, w, float(self.ent_coef))
+        return self.last_mix
+
+    def _mix_local(self, reward, novelty, entropy, coefs):
+        """The batch's channels as device f64, None where the coefficient is 0 (such a channel is never read)."""
+        dev = self.policy.flat.device
+        out = []
+        for name, t, a in zip(("reward", "novelty", "entropy"), (reward, novelty, entropy), coefs):
+            if a == 0.0:
+                out.append(None)
+                continue
+            if t is None:
+                raise ValueError("objective='mixed' with a non-zero %s coefficient needs the batch's %s (a Worker "
+                                 "without a strategy handler computes no novelty)" % (name, name))
+            t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t, np.float64))
+            out.append(t.to(device=dev, dtype=torch.float64).contiguous())
+        return out
+
+    def _step_batch_mixed(self, b, table):
+        """objective="mixed": fd_step_mix (one process, P <= 65536), else fd_grad_fused_mix + DSGD; sharded, one
+        all-gather of the three channels stacked, fd_grad_fused_mix on this rank's lanes, one all-reduce of g (the
+        one-collective moments form is not extended to three channels)."""
+        P = self.policy.num_params
+        coefs = self._mix_coefs()
+        ch = self._mix_local(b.reward, b.novelty, b.entropy, coefs)
+        if not self._distributed():
+            if P <= FUSED_STEP_MAX_P:
+                lr, lr_scale = self._lr()
+                slot = self._hist_slot()
+                engine.fd_step_mix(table, b.idx, ch, self._policy_values, coefs, b.sign, b.norm2, b.lanes_per_dir,
+                                   self.noise_std, self.policy.flat, lr, lr_scale, g=self.gradient_memory, out=self._out,
+                                   theta_hist=slot)
+                return self._after_update(slot)
+            g = engine.fd_grad_fused_mix(table, b.idx, ch, self._policy_values, coefs, 0, b.sign, b.norm2,
+                                         b.lanes_per_dir, self.noise_std, P, out=self.gradient_memory)
+            return self._apply(g)
+        ch_all, lane_lo = self._gather_channels(ch, b.reward.numel(), getattr(b, "rank_lanes", None))
+        g = engine.fd_grad_fused_mix(table, b.idx, ch_all, self._policy_values, coefs, lane_lo, b.sign, b.norm2,
+                                     b.lanes_per_dir, self.noise_std, P, out=self.gradient_memory)
+        fdist.allreduce_grad(g, self.process_group)
+        return self._apply(g)
+
+    def _gather_channels(self, ch, n, sizes):
+        """One all-gather of the active channels stacked [n, k] -> (each channel over all lanes, this rank's offset)."""
+        dev = self.policy.flat.device
+        active = [c for c in ch if c is not None]
+        stacked = torch.stack(active, dim=1).contiguous() if n else torch.zeros((0, len(active)), dtype=torch.float64,
+                                                                                  device=dev)
+        if sizes is None:
+            sizes = fdist.exchange_counts(n, dev, self.process_group)
+        k = len(active)
+        flat_all, lo = fdist.gather_rewards(stacked.reshape(-1), self.process_group, [int(s) * k for s in sizes])
+        cols = flat_all.reshape(-1, k)
+        it = iter(range(k))
+        return [None if c is None else cols[:, next(it)].contiguous() for c in ch], lo // k
+
     def _step_batch(self, b, policy_reward):
         table = self._table(b)
         if not np.all(b.sign_host != 0):
             raise ValueError("FDBatch for the learner must not contain eval lanes (sign 0)")
+        if self.objective == "mixed":
+            return self._step_batch_mixed(b, table)
         P = self.policy.num_params
         if not self._distributed():
             if P <= FUSED_STEP_MAX_P:   # the whole step in one launch: weights + gradient + DSGD
@@ -210,6 +288,9 @@ class FiniteDifferences(object):
         else:
             n2 = engine.fd_lambda_norms(table, idx_d, sign_d, None, self.noise_std, None, P)
         b = FDBatch(rewards, None, None, n2, idx_d, sign_d, idx, sign, self.epoch)
+        if self.objective == "mixed":
+            b.novelty = torch.as_tensor([float(r.novelty) for r in current], dtype=torch.float64, device=dev)
+            b.entropy = torch.as_tensor([float(r.entropy) for r in current], dtype=torch.float64, device=dev)
         return self._step_batch(b, policy_reward)
 
 
@@ -239,14 +320,23 @@ class FiniteDifferences(object):
         drift = torch.stack([self.dist_map[e] for e in epochs]).contiguous() if epochs else None
         slot_of = {e: k for k, e in enumerate(epochs)}
         rewards = torch.as_tensor([r.reward for r in keep], dtype=torch.float64, device=dev)
-        rewards_all, lane_lo = fdist.gather_rewards(rewards, self.process_group, sizes)
+        if self.objective == "mixed":
+            coefs = self._mix_coefs()
+            ch = self._mix_local(rewards, torch.as_tensor([float(r.novelty) for r in keep], dtype=torch.float64),
+                                 torch.as_tensor([float(r.entropy) for r in keep], dtype=torch.float64), coefs)
+            ch_all, lane_lo = self._gather_channels(ch, n, sizes) if self._distributed() else (ch, 0)
+        else:
+            rewards_all, lane_lo = fdist.gather_rewards(rewards, self.process_group, sizes)
         g = self.gradient_memory
         if n:
             idx_d = torch.as_tensor(idx_host, device=dev)
             sign_d = torch.as_tensor(np.array([int(getattr(r, "sign", 1) or 1) for r in keep], np.int8), device=dev)
             slot_d = torch.as_tensor(np.array([slot_of.get(r.epoch, -1) for r in keep], np.int32), device=dev)
             n2 = engine.fd_lambda_norms(table, idx_d, sign_d, slot_d, self.noise_std, drift, P)
-            if self.weighting == "centred_rank":   # ranks over all returns, v_i = lambda_i / ||lambda_i||^2
+            if self.objective == "mixed":
+                ones = torch.ones(n, dtype=torch.int8, device=dev)
+                coef = engine.fd_weights_mix(ch_all, self._policy_values, coefs, lane_lo, ones, n2, 1, 1.0)
+            elif self.weighting == "centred_rank":   # ranks over all returns, v_i = lambda_i / ||lambda_i||^2
                 coef = engine.rank_weights(rewards_all, lane_lo, n) / n2
             else:
                 ones = torch.ones(n, dtype=torch.int8, device=dev)

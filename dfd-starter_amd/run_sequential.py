@@ -105,10 +105,13 @@ class SequentialRunner(object):
                  omega_min_value=0, omega_max_value=1, omega_steps_to_min=25, omega_steps_to_max=75,
                  log_to_wandb=False, wandb_project="fd-starter", wandb_group=None, wandb_run_name=None,
                  noise_table_size=25_000_000, antithetic=False, episode_len=None, device=None, verbose=True,
-                 envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False, env_shape=None):
+                 envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False, env_shape=None,
+                 objective="reward"):
         """env_shape = (obs_dim, act_dim, discrete): instead of the env_id mapping, a SyntheticEnv of that shape
         (episode_len, default 1000) with the matching DiscretePolicy / MujocoPolicy -- any shape the engine's
-        runtime-shaped kernels take (obs_dim <= 64; act_dim <= 16 discrete, <= 8 continuous).  None: env_id."""
+        runtime-shaped kernels take (obs_dim <= 64; act_dim <= 16 discrete, <= 8 continuous).  None: env_id.
+        objective = "reward" (the reference's step) | "mixed": the learner weights every perturbation by
+        (1 - omega) z(reward) + omega z(novelty) + ent_coef z(entropy) (FiniteDifferences, build extension)."""
         if log_to_wandb:
             raise NotImplementedError("wandb logging is not part of the MI355X engine (no network)")
         self.verbose = verbose
@@ -161,7 +164,8 @@ class SequentialRunner(object):
                              random_seed=random_seed, eval_prob=eval_prob)
         self.learner = FiniteDifferences(self.policy, opt, self.omega, self.noise_source, noise_std=noise_std,
                                          batch_size=batch_size, ent_coef=ent_coef,
-                                         max_delayed_return=max_delayed_return)
+                                         max_delayed_return=max_delayed_return, objective=objective)
+        self.objective = objective
         self.policy_reward = 0
         self.policy_entropy = 0
         self.policy_novelty = 0
@@ -283,8 +287,8 @@ class SequentialRunner(object):
             lidx, sign = np.repeat(lidx, E), np.repeat(sign, E)
             if self.global_obs is not None and getattr(res, "obs_mean", None) is not None:
                 engine.obs_stats_merge(res.obs_mean, res.obs_m2, res.obs_count, *self.global_obs)
-            nov = self.worker.lane_novelty(idx_d, sign_d, table=None if rows is None else rows.table)  # worker.py:53
-            nov = np.zeros(len(lidx)) if nov is None else nov.cpu().numpy()
+            nov_d = self.worker.lane_novelty(idx_d, sign_d, table=None if rows is None else rows.table)  # worker.py:53
+            nov = np.zeros(len(lidx)) if nov_d is None else nov_d.cpu().numpy()
             rew = res.reward.cpu().numpy() + np.array([self.agent.rng.choice((-1e-12, 1e-12)) for _ in lidx])
             ent = res.entropy.cpu().numpy()
             steps = int(res.timesteps.sum().item())
@@ -305,7 +309,8 @@ class SequentialRunner(object):
             dev = self.policy.flat.device
             batch = FDBatch(torch.as_tensor(rew[:n_train], device=dev), res.entropy[:n_train],
                             res.timesteps[:n_train], res.norm2[:n_train], idx_d[:n_train], sign_d[:n_train],
-                            lidx[:n_train], sign[:n_train], self.learner.epoch, lanes_per_dir=lpd * E)
+                            lidx[:n_train], sign[:n_train], self.learner.epoch, lanes_per_dir=lpd * E,
+                            novelty=None if nov_d is None else nov_d[:n_train])   # the device tensor: no host trip
             if rows is not None:
                 batch.noise_table = rows.table
             update_magnitude = self.learner.step(batch, self.policy_reward, self.policy_novelty, self.policy_entropy)
@@ -331,7 +336,12 @@ class SequentialRunner(object):
                           "Noisy Novelty": float(np.mean(nov[:n_train])),
                           "Update Magnitude": update_magnitude,
                           "Omega": self.omega.omega}
-                self.history.append(dict(report, idx=idx_dirs, rewards=rew[:n_train]))
+                entry = dict(report, idx=idx_dirs, rewards=rew[:n_train])
+                if self.objective == "mixed":   # what the step weighted: the training lanes' other two channels
+                    entry.update(novelties=np.asarray(nov[:n_train], np.float64), entropies=np.asarray(
+                        ent[:n_train], np.float64), coefs=self.learner.last_mix,
+                        policy_values=self.learner._policy_values)
+                self.history.append(entry)
                 self._report_epoch(report)
 
     def _report_epoch(self, report):

@@ -293,6 +293,42 @@ int fdr_fd_step(fdr_ctx* ctx, const float* table, int64_t table_size, const int6
                 const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma, int32_t mode,
                 float* theta, double lr, double lr_scale, double* g, float* theta_hist, double* out, void* workspace,
                 int64_t workspace_bytes, fdr_stream stream);
+/* ---- the mixed objective: reward, novelty and entropy in one weight (NSRA-ES; the reference carries the
+ * combination at learner/finite_differences.py:40-48, switched off -- a build extension, opt-in) ---------------
+ * Channels c in (reward, novelty, entropy): an array over ALL n_all lanes, the policy's own value p_c and a
+ * coefficient a_c (the learner passes 1 - omega, omega, ent_coef).  With x_c = v_c - p_c (f64), m_c / sd_c its
+ * two-pass mean / population std over the n_all lanes (the workgroup tree of FDR_WEIGHT_ZSCORE) and
+ * z_c = x_c if sd_c == 0 else (x_c - m_c) / sd_c (standardize_arr, per channel):
+ *   w_i = sum over the ACTIVE channels, in the order reward, novelty, entropy, of  a_c * z_c[i]
+ * A channel with a_c == 0 is inactive: its array is never read (it may be NULL) and it adds no term, so the
+ * coefficients (1, 0, 0) give FDR_WEIGHT_ZSCORE's result bit for bit.  Everything else -- coefficients per
+ * direction, the gather, the chunk combine, NaN for an out-of-range offset, workspace, counters, out = g [P] -- is
+ * FDR_WEIGHT_ZSCORE's; the workspace size query takes mode FDR_WEIGHT_ZSCORE_MIX.  FDR_ERR_INVALID when all three
+ * coefficients are 0, one is not finite, or an active channel's array is NULL.  fdr_fd_grad_fused / fdr_fd_step
+ * refuse this mode: the channels do not fit their arguments. */
+#define FDR_WEIGHT_ZSCORE_MIX 3
+int fdr_fd_grad_fused_mix(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local,
+                          int32_t n_dirs, int64_t n_params, const double* rewards_all, const double* novelty_all,
+                          const double* entropy_all, int32_t n_all, double policy_reward, double policy_novelty,
+                          double policy_entropy, double coef_reward, double coef_novelty, double coef_entropy,
+                          int32_t lane_lo, const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir,
+                          float sigma, double* out, int64_t out_len, void* workspace, int64_t workspace_bytes,
+                          fdr_stream stream);
+/* fdr_fd_step with the mixed weights (single-process: n_all = n_dirs * lanes_per_dir). */
+int fdr_fd_step_mix(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                    int64_t n_params, const double* rewards_all, const double* novelty_all, const double* entropy_all,
+                    int32_t n_all, double policy_reward, double policy_novelty, double policy_entropy,
+                    double coef_reward, double coef_novelty, double coef_entropy, const int8_t* sign_local,
+                    const double* norm2_local, int32_t lanes_per_dir, float sigma, float* theta, double lr,
+                    double lr_scale, double* g, float* theta_hist, double* out, void* workspace,
+                    int64_t workspace_bytes, fdr_stream stream);
+/* fdr_fd_weights with the mixed weights: coef[d] for the staged gradient and for fdr_fd_grad_lambda (sign = +1,
+ * sigma = 1, lanes_per_dir = 1). */
+int fdr_fd_weights_mix(fdr_ctx* ctx, const double* rewards_all, const double* novelty_all, const double* entropy_all,
+                       int32_t n_all, double policy_reward, double policy_novelty, double policy_entropy,
+                       double coef_reward, double coef_novelty, double coef_entropy, int32_t lane_lo, int32_t n_local,
+                       const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                       double* coef, fdr_stream stream);
 /* The centred-rank weights alone: w [n_local] f64 for lanes [lane_lo, lane_lo + n_local) of rewards_all. */
 int fdr_rank_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, int32_t lane_lo, int32_t n_local,
                      double* w, fdr_stream stream);

@@ -1,5 +1,6 @@
 """Learner-kernel timings (GPU box): staged (fd_weights + fd_grad + dsgd) vs fused (fd_grad_fused [+ dsgd]) vs
-one-launch fdr_fd_step, at BASELINE config 3's shape (2048 directions x +-, P = 6092), HIP events over 50 calls.
+one-launch fdr_fd_step, and the mixed objective's three entry points (fd_grad_fused mix, fd_step mix, fd_weights_mix
+only), at BASELINE config 3's shape (2048 directions x +-, P = 6092), HIP events over 50 calls.
     python tools/learner_bench.py [n_dirs P]"""
 import os
 import sys
@@ -52,3 +53,11 @@ timeit("dsgd_step_ex (fused single WG)", lambda: engine.dsgd_step_ex(theta, g, F
 if P <= 65536:
     timeit("fd_step (one launch)", lambda: engine.fd_step(table, idx, rew, 0.0, sign, n2, 2, 0.02, theta, 0.01, 0.5,
                                                           g=g))
+# the mixed objective: random novelty / entropy channels, coefficients (0.6, 0.4, 0.05)
+chan = (rew, 0.3 * torch.randn(2 * n_dirs, dtype=torch.float64, device=dev).abs(),
+        1.4 + 0.05 * torch.randn(2 * n_dirs, dtype=torch.float64, device=dev))
+pol, mix = (0.0, 0.2, 1.3), (0.6, 0.4, 0.05)
+timeit("fd_grad_fused mix", lambda: engine.fd_grad_fused_mix(table, idx, chan, pol, mix, 0, sign, n2, 2, 0.02, P, out=g))
+if P <= 65536:
+    timeit("fd_step mix", lambda: engine.fd_step_mix(table, idx, chan, pol, mix, sign, n2, 2, 0.02, theta, 0.01, 0.5, g=g))
+timeit("fd_weights_mix only", lambda: engine.fd_weights_mix(chan, pol, mix, 0, sign, n2, 2, 0.02))

@@ -453,12 +453,30 @@ int64_t fdr_fd_grad_fused_out_len(int32_t mode, int64_t n_params, int32_t n_all)
   return -1;
 }
 
+// the optimizer arguments of fdr_opt_step / fdr_fd_step_opt / fdr_fd_step_mix_opt, validated
+struct OptCall {
+  int kind;
+  OptHyper h;
+  int64_t step;
+  float *state0, *state1;
+};
+static int opt_call(int32_t kind, double lr, double beta1, double beta2, double eps, double weight_decay,
+                    double momentum, double dampening, int32_t nesterov, int64_t step, float* state0, float* state1,
+                    OptCall* o) {
+  o->kind = kind;
+  o->h = OptHyper{lr, beta1, beta2, eps, weight_decay, momentum, dampening, nesterov ? 1 : 0};
+  o->step = step;
+  o->state0 = state0;
+  o->state1 = state1;
+  return opt_validate(kind, o->h, step, state0, state1);
+}
+
 static int fd_grad_fused_impl(const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
                               int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
                               int32_t lane_lo, const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir,
                               float sigma, int32_t mode, double* out, float* theta, double lr, double lr_scale,
                               float* hist, double* dsgd_out, void* workspace, int64_t workspace_bytes,
-                              fdr_stream stream, const MixChannels* mix = nullptr) {
+                              fdr_stream stream, const MixChannels* mix = nullptr, const OptCall* opt = nullptr) {
   if (!table || !out || n_params <= 0 || table_size < n_params || n_dirs < 0)
     return set_error(FDR_ERR_INVALID, "bad arguments");
   if (mode == FDR_WEIGHT_ZSCORE_MIX && !mix)
@@ -494,6 +512,13 @@ static int fd_grad_fused_impl(const float* table, int64_t table_size, const int6
   c.lr_scale = lr_scale;
   c.hist = hist;
   c.dsgd_out = dsgd_out;
+  if (opt) {
+    c.opt_kind = opt->kind;
+    c.opt = opt->h;
+    c.opt_step = opt->step;
+    c.state0 = opt->state0;
+    c.state1 = opt->state1;
+  }
   return launch_fd_grad_fused(c, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -564,6 +589,70 @@ int fdr_fd_step_mix(fdr_ctx* ctx, const float* table, int64_t table_size, const 
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, mx.v[0], n_all, mx.p[0], 0, sign_local,
                             norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_ZSCORE_MIX, g, theta, lr, lr_scale,
                             theta_hist, out, workspace, workspace_bytes, stream, &mx);
+}
+
+int64_t fdr_opt_workspace_bytes(int64_t n_params) { return opt_workspace_bytes(n_params); }
+
+int fdr_opt_step(fdr_ctx* ctx, int32_t kind, float* theta, const double* src, int32_t src_is_moments, int64_t n_params,
+                 double lr, double beta1, double beta2, double eps, double weight_decay, double momentum,
+                 double dampening, int32_t nesterov, int64_t step, float* state0, float* state1, double* g_out,
+                 float* theta_hist, double* out, void* workspace, int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  OptCall o;
+  const int rc = opt_call(kind, lr, beta1, beta2, eps, weight_decay, momentum, dampening, nesterov, step, state0,
+                          state1, &o);
+  if (rc) return rc;
+  if (!theta || !src || !out || n_params <= 0) return set_error(FDR_ERR_INVALID, "NULL theta / src / out, or n_params <= 0");
+  return launch_opt_step(kind, theta, src, src_is_moments ? 1 : 0, n_params, o.h, step, state0, state1, g_out,
+                         theta_hist, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int fdr_fd_step_opt(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                    int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
+                    const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                    int32_t mode, float* theta, int32_t kind, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, double momentum, double dampening, int32_t nesterov, int64_t step,
+                    float* state0, float* state1, double* g, float* theta_hist, double* out, void* workspace,
+                    int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  OptCall o;
+  const int rc = opt_call(kind, lr, beta1, beta2, eps, weight_decay, momentum, dampening, nesterov, step, state0,
+                          state1, &o);
+  if (rc) return rc;
+  if (!theta || !g || !out) return set_error(FDR_ERR_INVALID, "NULL theta / g / out");
+  if (mode == FDR_WEIGHT_MOMENTS)
+    return set_error(FDR_ERR_INVALID, "fdr_fd_step_opt takes z-score or centred-rank weights");
+  if (mode == FDR_WEIGHT_ZSCORE_MIX) return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_step_mix_opt");
+  if (n_all != n_dirs * lanes_per_dir)
+    return set_error(FDR_ERR_INVALID, "fdr_fd_step_opt is single-process: n_all = n_local");
+  return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, 0,
+                            sign_local, norm2_local, lanes_per_dir, sigma, mode, g, theta, 0.0, 0.0, theta_hist, out,
+                            workspace, workspace_bytes, stream, nullptr, &o);
+}
+
+int fdr_fd_step_mix_opt(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                        int64_t n_params, const double* rewards_all, const double* novelty_all,
+                        const double* entropy_all, int32_t n_all, double policy_reward, double policy_novelty,
+                        double policy_entropy, double coef_reward, double coef_novelty, double coef_entropy,
+                        const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                        float* theta, int32_t kind, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, double momentum, double dampening, int32_t nesterov, int64_t step,
+                        float* state0, float* state1, double* g, float* theta_hist, double* out, void* workspace,
+                        int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  OptCall o;
+  int rc = opt_call(kind, lr, beta1, beta2, eps, weight_decay, momentum, dampening, nesterov, step, state0, state1, &o);
+  if (rc) return rc;
+  if (!theta || !g || !out) return set_error(FDR_ERR_INVALID, "NULL theta / g / out");
+  MixChannels mx;
+  rc = mix_channels(rewards_all, novelty_all, entropy_all, policy_reward, policy_novelty, policy_entropy, coef_reward,
+                    coef_novelty, coef_entropy, mx);
+  if (rc) return rc;
+  if (n_all != n_dirs * lanes_per_dir)
+    return set_error(FDR_ERR_INVALID, "fdr_fd_step_mix_opt is single-process: n_all = n_local");
+  return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, mx.v[0], n_all, mx.p[0], 0, sign_local,
+                            norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_ZSCORE_MIX, g, theta, 0.0, 0.0, theta_hist,
+                            out, workspace, workspace_bytes, stream, &mx, &o);
 }
 
 int fdr_rank_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, int32_t lane_lo, int32_t n_local,

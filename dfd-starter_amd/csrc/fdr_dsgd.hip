@@ -185,6 +185,17 @@ __global__ __launch_bounds__(256) void moments_to_grad_kernel(const double* __re
     g[p] = grad_elem(src, P, p, true, m, sd);
 }
 
+// the moments form's g at any P: the statistics into stats [2], then g = (A - m B) / sd into g_out (also the first
+// half of fdr_optim.hip's launch_opt_step)
+int launch_moments_to_grad(const double* src, int64_t P, double* stats, double* g_out, hipStream_t stream) {
+  hipLaunchKernelGGL(moment_stats_kernel, dim3(1), dim3(1024), 0, stream, src, P, stats);
+  int rc = check_launch("moment_stats_kernel");
+  if (rc) return rc;
+  const int rb = (int)std::min<int64_t>((P + 255) / 256, 2048);
+  hipLaunchKernelGGL(moments_to_grad_kernel, dim3(rb), dim3(256), 0, stream, src, P, stats, g_out);
+  return check_launch("moments_to_grad_kernel");
+}
+
 int launch_dsgd_ex(float* theta, const double* src, int mom, int64_t P, double lr, double lr_scale, double* g_out,
                    double* out, void* ws, int64_t ws_bytes, hipStream_t stream) {
   if (P <= kDsgdFusedMaxP) {
@@ -196,13 +207,7 @@ int launch_dsgd_ex(float* theta, const double* src, int mom, int64_t P, double l
     if (!g_out) return set_error(FDR_ERR_INVALID, "moments form needs g_out for large P");
     if (ws == nullptr || ws_bytes < dsgd_workspace_bytes(P))
       return set_error(FDR_ERR_WORKSPACE, "dsgd workspace too small");
-    double* stats = DsgdWs(ws).stats;
-    hipLaunchKernelGGL(moment_stats_kernel, dim3(1), dim3(1024), 0, stream, src, P, stats);
-    int rc = check_launch("moment_stats_kernel");
-    if (rc) return rc;
-    const int rb = (int)std::min<int64_t>((P + 255) / 256, 2048);
-    hipLaunchKernelGGL(moments_to_grad_kernel, dim3(rb), dim3(256), 0, stream, src, P, stats, g_out);
-    rc = check_launch("moments_to_grad_kernel");
+    const int rc = launch_moments_to_grad(src, P, DsgdWs(ws).stats, g_out, stream);
     if (rc) return rc;
     g = g_out;
   }

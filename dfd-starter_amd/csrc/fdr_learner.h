@@ -1,6 +1,6 @@
 // Internal (non-ABI) host interface of the learner-side units behind the C ABI (fdr_api.hip): the launchers and
-// workspace queries of fdr_learner.hip, fdr_learner_fused.hip, fdr_dsgd.hip, fdr_novelty.hip and fdr_mlp_vbn.hip,
-// and the two structs that cross to their kernels by value (LambdaRow, FdArgs).
+// workspace queries of fdr_learner.hip, fdr_learner_fused.hip, fdr_dsgd.hip, fdr_optim.hip, fdr_novelty.hip and
+// fdr_mlp_vbn.hip, and the two structs that cross to their kernels by value (LambdaRow, FdArgs).
 #pragma once
 #include "fdr_internal.h"
 
@@ -98,6 +98,12 @@ struct FdMixArgs {
   FdArgs fd;
   MixChannels mix;
 };
+// A torch.optim step's hyperparameters as torch holds them (Python floats); fdr_optim.hip forms the kernel's f32
+// scalars from them and the step count.
+struct OptHyper {
+  double lr, beta1, beta2, eps, weight_decay, momentum, dampening;
+  int nesterov;
+};
 struct FusedCall {
   FdArgs fd;             // table .. sigma and out
   int mode;              // FDR_WEIGHT_*
@@ -107,6 +113,11 @@ struct FusedCall {
   double lr, lr_scale;
   float* hist;           // theta_new also goes here (the learner's policy_history), or NULL
   double* dsgd_out;      // [||d theta||, ||fl32(-g)||]
+  // fdr_fd_step_opt: opt_kind != 0 applies that optimizer (FDR_OPT_*) in place of DSGD; lr / lr_scale are not read
+  int opt_kind;
+  OptHyper opt;
+  int64_t opt_step;      // the step count including this step (torch's state["step"] after it)
+  float *state0, *state1;
 };
 int64_t fused_workspace_bytes(int n_dirs, int n_local, int64_t P, int mode);
 int64_t fused_counter_bytes(int n_dirs, int64_t P);
@@ -117,6 +128,22 @@ int launch_rank_weights(const double* r_all, int n_all, int lo, int n_local, dou
 int64_t dsgd_workspace_bytes(int64_t P);
 int launch_dsgd_ex(float* theta, const double* src, int mom, int64_t P, double lr, double lr_scale, double* g_out,
                    double* out, void* ws, int64_t ws_bytes, hipStream_t stream);
+// moment_stats_kernel + moments_to_grad_kernel: stats [2] <- mean, sd of the summed r' slots, g_out <- (A - m B) / sd
+int launch_moments_to_grad(const double* src, int64_t P, double* stats, double* g_out, hipStream_t stream);
+
+// ---- fdr_optim.hip ----
+constexpr int64_t kOptCounterBytes = 256;  // the ticket counter at the head of the standalone step's workspace
+int64_t opt_workspace_bytes(int64_t P);
+// FDR_ERR_INVALID naming the offending field, or FDR_OK; no device work
+int opt_validate(int kind, const OptHyper& h, int64_t step, const float* state0, const float* state1);
+// opt_apply_cb_kernel<kind> alone: gpart / upart [col_blocks] each, cnt one zeroed counter (left zero)
+int launch_opt_apply(int kind, float* theta, const double* g, int64_t P, const OptHyper& h, int64_t step,
+                     float* state0, float* state1, float* hist, double* gpart, double* upart, unsigned* cnt,
+                     double* out, hipStream_t stream);
+// from g or (src_is_moments) the summed moments, any P
+int launch_opt_step(int kind, float* theta, const double* src, int src_is_moments, int64_t P, const OptHyper& h,
+                    int64_t step, float* state0, float* state1, double* g_out, float* hist, double* out, void* ws,
+                    int64_t ws_bytes, hipStream_t stream);
 
 // ---- fdr_novelty.hip ----
 int launch_strategy_dist(const float* S, int n, const float* B, int H, int Z, int D, int kind, double* dists,

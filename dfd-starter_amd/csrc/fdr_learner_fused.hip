@@ -1,6 +1,7 @@
 // fdr_learner_fused.hip -- the fused learner step: weighting, noise-weighted gradient and chunk combine in one launch
 // (fd_grad_fused_kernel; fd_grad_fused_mix_kernel for the reward / novelty / entropy objective), the DSGD that can
-// follow it in the same call (dsgd_apply_cb_kernel), centred-rank weights.
+// follow it in the same call (dsgd_apply_cb_kernel; fdr_optim.hip's opt_apply_cb_kernel for Adam / AdamW / SGD),
+// centred-rank weights.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,28 +36,7 @@ namespace fdr {
 constexpr int kFusedRows = 64;       // table rows per pass: loads in flight per thread
 constexpr int kFusedMaxRows = 1024;  // directions per chunk (LDS coefficient arrays)
 
-// handed-off payload is stored write-through (sc1: an agent-scope relaxed atomic store), so the ticket needs
-// no release fence (cdna_hip_programming.md Guideline 16 R1)
-__device__ __forceinline__ void store_wt(double* p, double v) {
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void publish_and_ticket(unsigned* cnt, unsigned need, int* s_flag) {
-  // every storing wave drains its sc1 stores, the workgroup meets, ONE lane takes the ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == need - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *s_flag = last;
-  }
-  __syncthreads();
-}
+// store_wt / publish_and_ticket: fdr_reduce.h (shared with opt_apply_cb_kernel, fdr_optim.hip)
 
 // sum over k < n of base[k * stride] in k order, 16 loads in flight
 __device__ __forceinline__ double sum_slabs(const double* base, int64_t stride, int n) {
@@ -642,7 +622,7 @@ int launch_fd_grad_fused(const FusedCall& c, void* ws, int64_t ws_bytes, hipStre
   a.cnt = reinterpret_cast<unsigned*>(w);
   double* gsq = reinterpret_cast<double*>(w + cnt_b);
   double* upart = reinterpret_cast<double*>(w + cnt_b + cb_b);
-  a.gsq = c.theta ? gsq : nullptr;
+  a.gsq = c.theta && !c.opt_kind ? gsq : nullptr;  // opt_apply_cb_kernel sums its own fl32(-g)^2
   a.w = reinterpret_cast<double*>(w + cnt_b + 2 * cb_b);
   a.partial = reinterpret_cast<double*>(w + cnt_b + 2 * cb_b + w_b);
   const dim3 grid(f.col_blocks, f.n_chunks);
@@ -667,6 +647,9 @@ int launch_fd_grad_fused(const FusedCall& c, void* ws, int64_t ws_bytes, hipStre
   }
   int rc = check_launch("fd_grad_fused_kernel");
   if (rc || !c.theta) return rc;
+  if (c.opt_kind)  // fdr_fd_step_opt: the same regions and counter, the optimizer's apply in DSGD's place
+    return launch_opt_apply(c.opt_kind, c.theta, a.out, P, c.opt, c.opt_step, c.state0, c.state1, c.hist, gsq, upart,
+                            a.cnt + f.col_blocks, c.dsgd_out, stream);
   hipLaunchKernelGGL(dsgd_apply_cb_kernel, dim3(f.col_blocks), dim3(256), 0, stream, c.theta, a.out, P, gsq,
                      f.col_blocks, c.lr, c.lr_scale, c.hist, upart, a.cnt + f.col_blocks, c.dsgd_out);
   return check_launch("dsgd_apply_cb_kernel");

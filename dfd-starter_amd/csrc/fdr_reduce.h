@@ -37,4 +37,29 @@ inline __device__ double block_sum_1024(double v, double* red) {
   return s;
 }
 
+// ---- in-launch hand-off between workgroups (the ticket of fd_grad_fused_kernel, dsgd_apply_cb_kernel and
+// opt_apply_cb_kernel) ----
+// handed-off payload is stored write-through (sc1: an agent-scope relaxed atomic store), so the ticket needs
+// no release fence (cdna_hip_programming.md Guideline 16 R1)
+__device__ __forceinline__ void store_wt(double* p, double v) {
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v),
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void publish_and_ticket(unsigned* cnt, unsigned need, int* s_flag) {
+  // every storing wave drains its sc1 stores, the workgroup meets, ONE lane takes the ticket
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = prev == need - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *s_flag = last;
+  }
+  __syncthreads();
+}
+
 }  // namespace fdr

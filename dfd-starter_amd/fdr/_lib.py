@@ -18,6 +18,7 @@ FDR_ROLLOUT_PAIR, FDR_ROLLOUT_SINGLE, FDR_ROLLOUT_AUTO, FDR_ROLLOUT_WIDE = 0, 1,
 FDR_ROLLOUT_GENERIC = 4   # the runtime-shaped kernel family at every shape
 FDR_WEIGHT_ZSCORE, FDR_WEIGHT_CENTERED_RANK, FDR_WEIGHT_MOMENTS = 0, 1, 2
 FDR_WEIGHT_ZSCORE_MIX = 3   # reward / novelty / entropy: fdr_fd_grad_fused_mix, fdr_fd_step_mix
+FDR_OPT_ADAM, FDR_OPT_ADAMW, FDR_OPT_SGD = 1, 2, 3   # fdr_opt_step, fdr_fd_step_opt, fdr_fd_step_mix_opt
 FDR_LOADER_LANE, FDR_LOADER_PAIR, FDR_LOADER_DYN = 0, 1, 2   # include/fdr_diag.h
 
 EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy", "fdr_ctx_device",
@@ -38,7 +39,8 @@ EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy",
            "fdr_ctx_impala_profile_read", "fdr_ctx_impala_debug_clock", "fdr_noise_draw_indices",
            "fdr_impala_bn_refresh_workspace_bytes", "fdr_impala_bn_refresh", "fdr_atari_strategies_workspace_bytes",
            "fdr_atari_strategies", "fdr_atari_bn_refresh_workspace_bytes", "fdr_atari_bn_refresh",
-           "fdr_diag_theta_prime", "fdr_fd_grad_fused_mix", "fdr_fd_step_mix", "fdr_fd_weights_mix")
+           "fdr_diag_theta_prime", "fdr_fd_grad_fused_mix", "fdr_fd_step_mix", "fdr_fd_weights_mix",
+           "fdr_opt_workspace_bytes", "fdr_opt_step", "fdr_fd_step_opt", "fdr_fd_step_mix_opt")
 
 
 class FDRError(RuntimeError):
@@ -149,6 +151,15 @@ def _load():
                                            F32, P, F64, F64, P, P, P, P, I64, P]),
         "fdr_fd_weights_mix": (ctypes.c_int, [P, P, P, P, I32, F64, F64, F64, F64, F64, F64, I32, I32, P, P, I32, F32, P,
                                               P]),
+        # the optimizer block: kind, lr, beta1, beta2, eps, weight_decay, momentum, dampening, nesterov, step, state0, state1
+        "fdr_opt_workspace_bytes": (I64, [I64]),
+        "fdr_opt_step": (ctypes.c_int, [P, I32, P, P, I32, I64, F64, F64, F64, F64, F64, F64, F64, I32, I64, P, P, P, P,
+                                        P, P, I64, P]),
+        "fdr_fd_step_opt": (ctypes.c_int, [P, P, I64, P, I32, I64, P, I32, F64, P, P, I32, F32, I32, P, I32, F64, F64,
+                                           F64, F64, F64, F64, F64, I32, I64, P, P, P, P, P, P, I64, P]),
+        "fdr_fd_step_mix_opt": (ctypes.c_int, [P, P, I64, P, I32, I64, P, P, P, I32, F64, F64, F64, F64, F64, F64, P, P,
+                                               I32, F32, P, I32, F64, F64, F64, F64, F64, F64, F64, I32, I64, P, P, P, P,
+                                               P, P, I64, P]),
         "fdr_dsgd_step_ex": (ctypes.c_int, [P, P, P, I32, I64, F64, F64, P, P, P, I64, P]),
         "fdr_dsgd_step": (ctypes.c_int, [P, P, P, I64, F64, F64, P, P, I64, P]),
         "fdr_atari_env_frames": (ctypes.c_int, [ctypes.c_uint64, I64, I32, I32, P, P]),

@@ -439,6 +439,90 @@ def dsgd_step_ex(theta, src, moments, lr, lr_scale, g_out=None, out=None):
     return out
 
 
+OPT_KINDS = {"adam": _lib.FDR_OPT_ADAM, "adamw": _lib.FDR_OPT_ADAMW, "sgd": _lib.FDR_OPT_SGD}
+
+
+class OptSpec(object):
+    """One torch.optim step for fdr_opt_step / fdr_fd_step_opt: kind "adam" | "adamw" | "sgd", the hyperparameters as
+    torch's param group holds them, step = the count including this step, and the f32 [P] state rows (adam / adamw:
+    exp_avg, exp_avg_sq; sgd with momentum: momentum_buffer, None)."""
+
+    def __init__(self, kind, lr, step, state0=None, state1=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 momentum=0.0, dampening=0.0, nesterov=False):
+        self.kind = OPT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        self.lr, self.step, self.state0, self.state1 = float(lr), int(step), state0, state1
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.momentum, self.dampening, self.nesterov = float(momentum), float(dampening), bool(nesterov)
+
+    def args(self):
+        """The optimizer block of the C calls, in order."""
+        return (self.kind, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.momentum,
+                self.dampening, 1 if self.nesterov else 0, self.step, _p(self.state0), _p(self.state1))
+
+    def check(self, P, dev):
+        for t in (self.state0, self.state1):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != P or not t.is_contiguous()
+                                  or t.device != dev):
+                raise ValueError("optimizer state rows are contiguous f32 [P] on theta's device")
+
+
+def opt_step(theta, src, moments, opt, g_out=None, out=None, theta_hist=None):
+    """An Adam / AdamW / SGD step (fdr_opt_step) from g (moments=False) or from summed moments (g written to g_out);
+    any P.  Returns device f64[2] = (||d theta||, ||fl32(-g)||)."""
+    _check_dev(theta, src, g_out, theta_hist)
+    dev = theta.device
+    P = theta.numel()
+    opt.check(P, dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = _workspace("opt", lib.fdr_opt_workspace_bytes(P), dev, zeroed=True)   # the ticket counter starts at zero
+    check(lib.fdr_opt_step(_c(dev), opt.kind, _p(theta), _p(src), 1 if moments else 0, P, *opt.args()[1:], _p(g_out),
+                           _p(theta_hist), _p(out), _p(ws), ws.numel(), _stream(dev)), "fdr_opt_step")
+    return out
+
+
+def fd_step_opt(table, idx_local, rewards, policy_reward, sign_local, norm2_local, lanes_per_dir, sigma, theta, opt,
+                mode="zscore", g=None, out=None, theta_hist=None):
+    """fd_step with the optimizer's apply launch in DSGD's place (fdr_fd_step_opt): weights + gradient (-> g) in one
+    launch, opt (an OptSpec) on theta and its state in place in a second.  Returns device f64[2]."""
+    _check_dev(table, idx_local, rewards, sign_local, norm2_local, theta, g, theta_hist)
+    dev = table.device
+    P = theta.numel()
+    opt.check(P, dev)
+    n_dirs = idx_local.numel() // int(lanes_per_dir)
+    m = WEIGHT_MODES[mode]
+    if g is None:
+        g = torch.empty(P, dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = _fused_workspace(m, n_dirs, lanes_per_dir, P, dev)
+    check(lib.fdr_fd_step_opt(_c(dev), _p(table), table.numel(), _p(idx_local), n_dirs, P, _p(rewards), rewards.numel(),
+                              float(policy_reward), _p(sign_local), _p(norm2_local), int(lanes_per_dir), float(sigma), m,
+                              _p(theta), *opt.args(), _p(g), _p(theta_hist), _p(out), _p(ws), ws.numel(), _stream(dev)),
+          "fdr_fd_step_opt")
+    return out
+
+
+def fd_step_mix_opt(table, idx_local, channels, policy_values, coefs, sign_local, norm2_local, lanes_per_dir, sigma,
+                    theta, opt, g=None, out=None, theta_hist=None):
+    """fd_step_mix with the optimizer's apply launch in DSGD's place (fdr_fd_step_mix_opt)."""
+    channels, dev, n_all, vals = _mix_channels(channels, policy_values, coefs)
+    _check_dev(table, idx_local, sign_local, norm2_local, theta, g, theta_hist, channels[0], channels[1], channels[2])
+    P = theta.numel()
+    opt.check(P, dev)
+    n_dirs = idx_local.numel() // int(lanes_per_dir)
+    if g is None:
+        g = torch.empty(P, dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = _fused_workspace(_lib.FDR_WEIGHT_ZSCORE_MIX, n_dirs, lanes_per_dir, P, dev)
+    check(lib.fdr_fd_step_mix_opt(_c(dev), _p(table), table.numel(), _p(idx_local), n_dirs, P, _p(channels[0]),
+                                  _p(channels[1]), _p(channels[2]), n_all, *vals, _p(sign_local), _p(norm2_local),
+                                  int(lanes_per_dir), float(sigma), _p(theta), *opt.args(), _p(g), _p(theta_hist),
+                                  _p(out), _p(ws), ws.numel(), _stream(dev)), "fdr_fd_step_mix_opt")
+    return out
+
+
 def fd_grad(table, idx_dirs, coef, n_params, g=None):
     _check_dev(table, idx_dirs, coef)
     dev = table.device

@@ -24,6 +24,17 @@ fdr_fd_grad_fused_mix in place of the two calls above, fdr_fd_weights_mix on the
 takes the gather form (one all-gather of the three channels stacked, one all-reduce of g).  ``objective="reward"``,
 the default, is the reference's step; "mixed" with omega = 0 and ent_coef = 0 equals it bit for bit.
 
+``gradient_optimizer`` is honoured as the reference honours it (finite_differences.py:51-59: any torch.optim
+optimizer steps on ``policy.set_grad_from_flat(-g)``).  describe_optimizer() sorts it once into one of three routes:
+"dsgd" (the two calls above, unchanged); "device" -- torch.optim.Adam / AdamW / SGD over exactly the policy's
+parameters in one group, float lr, no amsgrad / maximize / capturable / differentiable: the optimizer's own
+single-tensor step runs in the apply launch (fdr_fd_step_opt / fdr_fd_step_mix_opt, or fdr_opt_step after a reduced
+gradient / moments), the hyperparameters read from ``param_groups[0]`` at every step (an LR scheduler works), its
+state two flat f32 [P] rows owned by the learner and published into ``gradient_optimizer.state`` as per-parameter
+views under torch's keys (state_dict() reports them; a load_state_dict is copied in before the next step); "generic" --
+anything else: g on the device, then literally zero_grad(), set_grad_from_flat(-g), optimizer.step() (slow, correct for
+any optimizer).
+
 Returns carry a current epoch in the synchronous engine; returns from an older epoch (the
 reference's async server mode) add the parameter drift theta_epoch - theta_now to lambda
 (finite_differences.py:66-92) -- fdr_fd_lambda_norms / fdr_fd_grad_lambda, single-process or sharded
@@ -41,6 +52,53 @@ from utils.noise_sources import HostNoiseRows, is_host_noise, require_noise_sour
 from .fd_return import FDBatch
 
 FUSED_STEP_MAX_P = 1 << 16   # fdr_fd_step fuses DSGD into the gradient launch up to this many parameters
+
+
+class OptimizerRoute(object):
+    """How the learner applies its gradient_optimizer: route "dsgd" | "device" | "generic"; kind "adam" | "adamw" |
+    "sgd" on the device route; why: what sent an Adam / AdamW / SGD to the generic route (None otherwise)."""
+
+    def __init__(self, route, kind=None, why=None):
+        self.route, self.kind, self.why = route, kind, why
+
+    def __repr__(self):
+        return "OptimizerRoute(%r, %r, %r)" % (self.route, self.kind, self.why)
+
+
+def _tiles_flat(params, flat):
+    """Do the parameters, in order, tile the policy's flat f32 buffer exactly?"""
+    off = 0
+    for p in params:
+        d = p.data
+        if d.dtype != torch.float32 or d.device != flat.device or not d.is_contiguous() \
+                or d.data_ptr() != flat.data_ptr() + 4 * off:
+            return False
+        off += d.numel()
+    return off == flat.numel()
+
+
+def describe_optimizer(policy, opt):
+    """Sort a gradient optimizer into the learner's routes (see the module docstring).  Exact classes only: a subclass
+    may override step()."""
+    if isinstance(opt, DSGD):
+        return OptimizerRoute("dsgd")
+    if type(opt) not in (torch.optim.Adam, torch.optim.AdamW, torch.optim.SGD):
+        return OptimizerRoute("generic")
+    if len(opt.param_groups) != 1:
+        return OptimizerRoute("generic", why="%d param groups" % len(opt.param_groups))
+    gr = opt.param_groups[0]
+    if not _tiles_flat(gr["params"], policy.flat):
+        return OptimizerRoute("generic", why="parameters other than the policy's")
+    for flag in ("amsgrad", "maximize", "capturable", "differentiable"):
+        if gr.get(flag):
+            return OptimizerRoute("generic", why=flag)
+    scalars = [gr["lr"], gr["weight_decay"]] + (list(gr["betas"]) + [gr["eps"]] if "betas" in gr else
+                                                [gr["momentum"], gr["dampening"]])
+    if any(torch.is_tensor(x) for x in scalars):
+        return OptimizerRoute("generic", why="tensor hyperparameter")
+    if type(opt) is torch.optim.SGD:
+        return OptimizerRoute("device", "sgd")
+    return OptimizerRoute("device", "adamw" if gr.get("decoupled_weight_decay") else "adam")
 
 
 class FiniteDifferences(object):
@@ -74,6 +132,9 @@ class FiniteDifferences(object):
         self.policy_history = [(policy.flat.detach().clone(), 0)]
         self.dist_map = {0: None}
         self.using_dsgd = isinstance(gradient_optimizer, DSGD)
+        self.opt_route = describe_optimizer(policy, gradient_optimizer)
+        self._opt_rows = None   # device route: the optimizer state, f32 [2, P] (exp_avg | exp_avg_sq; momentum_buffer)
+        self._opt_t = 0         # ... and the steps it has taken (torch's state["step"])
         P = policy.num_params
         self.gradient_memory = torch.zeros(P, dtype=torch.float64, device=policy.flat.device)
         self._out = torch.zeros(2, dtype=torch.float64, device=policy.flat.device)
@@ -92,7 +153,8 @@ class FiniteDifferences(object):
         if out is None:
             return 0
         upd, gnorm = out.tolist()
-        assert gnorm > 0, "DSGD ENCOUNTERED GRADIENT WITH NORM OF ZERO"   # dynamic_sgd.py:28
+        if self.using_dsgd:
+            assert gnorm > 0, "DSGD ENCOUNTERED GRADIENT WITH NORM OF ZERO"   # dynamic_sgd.py:28
         return upd
 
     def step_async(self, batch, policy_reward, policy_novelty, policy_entropy):
@@ -144,7 +206,13 @@ class FiniteDifferences(object):
         coefs = self._mix_coefs()
         ch = self._mix_local(b.reward, b.novelty, b.entropy, coefs)
         if not self._distributed():
-            if P <= FUSED_STEP_MAX_P:
+            if P <= FUSED_STEP_MAX_P and self.opt_route.route == "device":
+                slot = self._hist_slot()
+                engine.fd_step_mix_opt(table, b.idx, ch, self._policy_values, coefs, b.sign, b.norm2, b.lanes_per_dir,
+                                       self.noise_std, self.policy.flat, self._opt_spec(), g=self.gradient_memory,
+                                       out=self._out, theta_hist=slot)
+                return self._after_opt(slot)
+            if P <= FUSED_STEP_MAX_P and self.using_dsgd:
                 lr, lr_scale = self._lr()
                 slot = self._hist_slot()
                 engine.fd_step_mix(table, b.idx, ch, self._policy_values, coefs, b.sign, b.norm2, b.lanes_per_dir,
@@ -182,7 +250,13 @@ class FiniteDifferences(object):
             return self._step_batch_mixed(b, table)
         P = self.policy.num_params
         if not self._distributed():
-            if P <= FUSED_STEP_MAX_P:   # the whole step in one launch: weights + gradient + DSGD
+            if P <= FUSED_STEP_MAX_P and self.opt_route.route == "device":   # the same two launches, the apply swapped
+                slot = self._hist_slot()
+                engine.fd_step_opt(table, b.idx, b.reward, policy_reward, b.sign, b.norm2, b.lanes_per_dir,
+                                   self.noise_std, self.policy.flat, self._opt_spec(), mode=self.weighting,
+                                   g=self.gradient_memory, out=self._out, theta_hist=slot)
+                return self._after_opt(slot)
+            if P <= FUSED_STEP_MAX_P and self.using_dsgd:   # the whole step in one launch: weights + gradient + DSGD
                 lr, lr_scale = self._lr()
                 slot = self._hist_slot()
                 engine.fd_step(table, b.idx, b.reward, policy_reward, b.sign, b.norm2, b.lanes_per_dir, self.noise_std,
@@ -193,7 +267,8 @@ class FiniteDifferences(object):
                                      self.noise_std, P, mode=self.weighting, out=self.gradient_memory)
             return self._apply(g)
         sizes = getattr(b, "rank_lanes", None)
-        if self.weighting == "zscore" and self.one_collective and sizes is not None and b.lanes_per_dir == 2:
+        if self.weighting == "zscore" and self.one_collective and sizes is not None and b.lanes_per_dir == 2 \
+                and self.opt_route.route != "generic":   # the generic route takes g itself: the gather form below
             # the split is known on every rank (Worker.evaluate's lane_range): [A | B | n | r' slots], ONE all-reduce.
             # Antithetic only: there B = 0 exactly, so A - m B carries no cancellation; one-sided batches with
             # near-constant returns (|m| >> sd) would lose digits in it, and take the exact gather path below.
@@ -213,10 +288,91 @@ class FiniteDifferences(object):
         return self._apply(g)
 
     def _lr(self):
-        if self.using_dsgd:
-            self.gradient_optimizer.adjust_lr(self.omega)
-            return self.gradient_optimizer.lr, self.gradient_optimizer.lr_scale
-        return self.gradient_optimizer.param_groups[0]["lr"], 1.0
+        """DSGD's (lr, lr_scale); adjust_lr is DSGD's alone (finite_differences.py:51-52)."""
+        self.gradient_optimizer.adjust_lr(self.omega)
+        return self.gradient_optimizer.lr, self.gradient_optimizer.lr_scale
+
+    # ---- the device route's optimizer state --------------------------------------------------------------------
+    def _opt_keys(self):
+        if self.opt_route.kind == "sgd":
+            return ("momentum_buffer",) if self.gradient_optimizer.param_groups[0]["momentum"] != 0 else ()
+        return ("exp_avg", "exp_avg_sq")
+
+    def _sync_opt_state(self, keys):
+        """The learner's rows and gradient_optimizer.state agree before a step: state tensors that are not views of
+        the rows (a load_state_dict, a step the caller ran) are copied in and the step count taken from them; keys
+        that went missing after publication (state cleared) restart from zero, as torch would; then fresh views."""
+        opt = self.gradient_optimizer
+        flat = self.policy.flat
+        first = self._opt_rows is None
+        if first:
+            self._opt_rows = torch.zeros((2, flat.numel()), dtype=torch.float32, device=flat.device)
+        rows = self._opt_rows
+        params = opt.param_groups[0]["params"]
+        foreign = missing = False
+        off = 0
+        for p in params:
+            st = opt.state[p] if p in opt.state else {}
+            n = p.numel()
+            for r, k in enumerate(keys):
+                t = st.get(k)
+                if t is None:
+                    missing = True
+                elif t.data_ptr() != rows[r].data_ptr() + 4 * off or t.dtype != torch.float32 or t.device != flat.device:
+                    rows[r, off:off + n].copy_(t.detach().reshape(-1).to(device=flat.device, dtype=torch.float32))
+                    foreign = True
+            off += n
+        if not (first or foreign or missing):
+            return
+        if foreign:
+            steps = [opt.state[p]["step"] for p in params if p in opt.state and "step" in opt.state[p]]
+            self._opt_t = int(float(steps[0])) if steps else max(self._opt_t, 1)
+        elif missing:
+            if not first:
+                rows.zero_()
+            self._opt_t = 0
+        off = 0
+        for p in params:
+            st = opt.state[p]
+            n = p.numel()
+            for r, k in enumerate(keys):
+                st[k] = rows[r, off:off + n].view_as(p)
+            if self.opt_route.kind != "sgd":
+                st["step"] = torch.tensor(float(self._opt_t))
+            off += n
+
+    def _opt_spec(self):
+        """This step's OptSpec: the hyperparameters as param_groups[0] holds them now, the step count, the rows."""
+        keys = self._opt_keys()
+        if keys:
+            self._sync_opt_state(keys)
+        gr = self.gradient_optimizer.param_groups[0]
+        rows = self._opt_rows
+        if self.opt_route.kind == "sgd":
+            return engine.OptSpec("sgd", gr["lr"], self._opt_t + 1, rows[0] if keys else None, None,
+                                  weight_decay=gr["weight_decay"], momentum=gr["momentum"], dampening=gr["dampening"],
+                                  nesterov=gr["nesterov"])
+        return engine.OptSpec(self.opt_route.kind, gr["lr"], self._opt_t + 1, rows[0], rows[1], betas=gr["betas"],
+                              eps=gr["eps"], weight_decay=gr["weight_decay"])
+
+    def _after_opt(self, hist=None):
+        self._opt_t += 1
+        if self.opt_route.kind != "sgd":
+            for p in self.gradient_optimizer.param_groups[0]["params"]:
+                self.gradient_optimizer.state[p]["step"].fill_(self._opt_t)
+        return self._after_update(hist)
+
+    def _apply_generic(self, g):
+        """The reference's literal sequence (finite_differences.py:51-59) on device tensors, for any optimizer."""
+        flat = self.policy.flat
+        old = flat.detach().clone()
+        self.gradient_optimizer.zero_grad()
+        neg = -g
+        self.policy.set_grad_from_flat(neg)
+        self.gradient_optimizer.step()
+        self._out[0] = torch.linalg.vector_norm((old - flat.detach()).double())
+        self._out[1] = torch.linalg.vector_norm(neg.float().double())
+        return self._after_update()
 
     def _hist_slot(self):
         if self._hist_ring is None:
@@ -234,6 +390,13 @@ class FiniteDifferences(object):
         return self._out
 
     def _apply(self, src, moments=False):
+        if self.opt_route.route == "device":
+            slot = self._hist_slot()
+            engine.opt_step(self.policy.flat, src, moments, self._opt_spec(),
+                            g_out=self.gradient_memory if moments else None, out=self._out, theta_hist=slot)
+            return self._after_opt(slot)
+        if self.opt_route.route == "generic":
+            return self._apply_generic(src)
         lr, lr_scale = self._lr()
         engine.dsgd_step_ex(self.policy.flat, src, moments, lr, lr_scale, g_out=self.gradient_memory if moments else None,
                             out=self._out)

@@ -106,8 +106,11 @@ class SequentialRunner(object):
                  log_to_wandb=False, wandb_project="fd-starter", wandb_group=None, wandb_run_name=None,
                  noise_table_size=25_000_000, antithetic=False, episode_len=None, device=None, verbose=True,
                  envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False, env_shape=None,
-                 objective="reward"):
-        """env_shape = (obs_dim, act_dim, discrete): instead of the env_id mapping, a SyntheticEnv of that shape
+                 objective="reward", opt_kwargs=None):
+        """opt_fn: DSGD (the reference runner's), or any torch.optim class -- opt_fn(policy.parameters(),
+        lr=learning_rate, **opt_kwargs); torch.optim.Adam / AdamW / SGD step inside the learner's apply launch, any
+        other optimizer through the learner's generic route (FiniteDifferences).
+        env_shape = (obs_dim, act_dim, discrete): instead of the env_id mapping, a SyntheticEnv of that shape
         (episode_len, default 1000) with the matching DiscretePolicy / MujocoPolicy -- any shape the engine's
         runtime-shaped kernels take (obs_dim <= 64; act_dim <= 16 discrete, <= 8 continuous).  None: env_id.
         objective = "reward" (the reference's step) | "mixed": the learner weights every perturbation by
@@ -146,7 +149,7 @@ class SequentialRunner(object):
         else:
             self.policy = MujocoPolicy(self.env.obs_dim, self.env.act_dim, seed=random_seed, device=self.device)
             dist_fn = math_helpers.gaussian_wasserstein_dist_from_strategies   # SURVEY finding 6 fixed
-        opt = opt_fn(self.policy.parameters(), lr=learning_rate)
+        opt = opt_fn(self.policy.parameters(), lr=learning_rate, **(opt_kwargs or {}))
         # noise_source: "table" (SharedNoiseTable, the GPU fast path: offsets into an HBM-resident table) or the
         # reference runner's default "rng" (run_sequential.py:89, RNGNoiseSource) / "simple": host noise sources,
         # theta' rows materialised per lane (slow, correct; utils/noise_sources.py HostNoiseRows)

@@ -380,6 +380,57 @@ int fdr_dsgd_step_ex(fdr_ctx* ctx, float* theta, const double* src, int32_t src_
                      double lr, double lr_scale, double* g_out, double* out, void* workspace, int64_t workspace_bytes,
                      fdr_stream stream);
 
+/* ---- torch.optim steps on the device: Adam, AdamW, SGD (learner/finite_differences.py:51-59 with any optimizer) ----
+ * grad = fl32(-g) (policy.set_grad_from_flat), then the optimizer's single-tensor step of torch/optim/adam.py,
+ * adamw.py, sgd.py (non-capturable, maximize = False, no amsgrad), every operation in f32, on theta [P] f32 and the
+ * f32 state rows in place:
+ *   FDR_OPT_ADAM   state0 = exp_avg m, state1 = exp_avg_sq v:  grad += wd theta (wd != 0);
+ *                  m <- lerp(m, grad, 1 - beta1);  v <- beta2 v + (1 - beta2) grad^2;
+ *                  theta <- theta - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *   FDR_OPT_ADAMW  theta <- theta (1 - lr wd) first, then FDR_OPT_ADAM without the L2 term
+ *   FDR_OPT_SGD    state0 = momentum_buffer b (state1 unused):  grad += wd theta (wd != 0);  momentum != 0:
+ *                  b <- grad at step == 1, else momentum b + (1 - dampening) grad;  grad <- grad + momentum b
+ *                  (nesterov) or b;  theta <- theta - lr grad.  momentum == 0 reads and writes no state.
+ * step: the step count INCLUDING this one (torch's state["step"] after the call; 1 on the first).  The scalars torch
+ * forms from Python floats (lr / (1 - beta1^step), sqrt(1 - beta2^step), 1 - lr wd, 1 - beta, 1 - dampening) are
+ * formed in double on the host and rounded to f32 once.  beta1, beta2, eps are not read by FDR_OPT_SGD; momentum,
+ * dampening, nesterov not by the Adam kinds.
+ * out (device f64[2]) = [||theta_old - theta_new||, ||fl32(-g)||], summed in f64 in column-block order.  theta_hist
+ * [P] f32 (nullable) also receives the new theta.
+ * FDR_ERR_INVALID before any device work, the field named in fdr_last_error(): unknown kind; step < 1; lr, eps,
+ * weight_decay or momentum negative or not finite; a beta outside [0, 1); a NULL state row the kind needs; nesterov
+ * with momentum == 0 or dampening != 0.
+ * fdr_opt_step: from g [P] f64, or (src_is_moments = 1) from the summed moments of FDR_WEIGHT_MOMENTS, g written to
+ * g_out [P] (required then) as fdr_dsgd_step_ex forms it; any P, one workgroup per 256 parameters.  workspace:
+ * fdr_opt_workspace_bytes(P) bytes whose first 256 (a ticket counter) must be zero before the first call on that
+ * workspace; every call leaves them zero. */
+#define FDR_OPT_ADAM 1
+#define FDR_OPT_ADAMW 2
+#define FDR_OPT_SGD 3
+int64_t fdr_opt_workspace_bytes(int64_t n_params);
+int fdr_opt_step(fdr_ctx* ctx, int32_t kind, float* theta, const double* src, int32_t src_is_moments, int64_t n_params,
+                 double lr, double beta1, double beta2, double eps, double weight_decay, double momentum,
+                 double dampening, int32_t nesterov, int64_t step, float* state0, float* state1, double* g_out,
+                 float* theta_hist, double* out, void* workspace, int64_t workspace_bytes, fdr_stream stream);
+/* fdr_fd_step / fdr_fd_step_mix with the optimizer's apply launch in DSGD's place: the same gradient launch, the
+ * same workspace and counters (no lr_scale: that is DSGD's). */
+int fdr_fd_step_opt(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                    int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
+                    const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                    int32_t mode, float* theta, int32_t kind, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, double momentum, double dampening, int32_t nesterov, int64_t step,
+                    float* state0, float* state1, double* g, float* theta_hist, double* out, void* workspace,
+                    int64_t workspace_bytes, fdr_stream stream);
+int fdr_fd_step_mix_opt(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                        int64_t n_params, const double* rewards_all, const double* novelty_all,
+                        const double* entropy_all, int32_t n_all, double policy_reward, double policy_novelty,
+                        double policy_entropy, double coef_reward, double coef_novelty, double coef_entropy,
+                        const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                        float* theta, int32_t kind, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, double momentum, double dampening, int32_t nesterov, int64_t step,
+                        float* state0, float* state1, double* g, float* theta_hist, double* out, void* workspace,
+                        int64_t workspace_bytes, fdr_stream stream);
+
 /* ---- strategy distances / novelty (utils/math_helpers.py:147-222, strategy/) -----------------
  * strategies [n, Z, D] f32 = get_strategy over the Z probe states for n policies (e.g. every
  * perturbed lane); archive [H, Z, D] f32.  d[i][h] = mean over z of

@@ -1,6 +1,7 @@
 """Learner-kernel timings (GPU box): staged (fd_weights + fd_grad + dsgd) vs fused (fd_grad_fused [+ dsgd]) vs
 one-launch fdr_fd_step, and the mixed objective's three entry points (fd_grad_fused mix, fd_step mix, fd_weights_mix
-only), at BASELINE config 3's shape (2048 directions x +-, P = 6092), HIP events over 50 calls.
+only), and the optimizer apply launches (opt_apply_cb_kernel beside dsgd_apply_cb_kernel), at BASELINE config 3's shape
+(2048 directions x +-, P = 6092), HIP events over 50 calls (1000 for the apply launches alone).
     python tools/learner_bench.py [n_dirs P]"""
 import os
 import sys
@@ -35,7 +36,9 @@ def timeit(name, fn, n=50):
         fn()
     e1.record()
     torch.cuda.synchronize()
-    print("%-40s %8.2f us / call" % (name, e0.elapsed_time(e1) * 1e3 / n), flush=True)
+    us = e0.elapsed_time(e1) * 1e3 / n
+    print("%-40s %8.2f us / call" % (name, us), flush=True)
+    return us
 
 
 def staged():
@@ -61,3 +64,19 @@ timeit("fd_grad_fused mix", lambda: engine.fd_grad_fused_mix(table, idx, chan, p
 if P <= 65536:
     timeit("fd_step mix", lambda: engine.fd_step_mix(table, idx, chan, pol, mix, sign, n2, 2, 0.02, theta, 0.01, 0.5, g=g))
 timeit("fd_weights_mix only", lambda: engine.fd_weights_mix(chan, pol, mix, 0, sign, n2, 2, 0.02))
+
+# the apply launch alone: the optimizers' opt_apply_cb_kernel directly (fdr_opt_step from g is that one launch);
+# dsgd_apply_cb_kernel only runs behind the gradient launch, so it is fd_step minus fd_grad_fused on the same build
+m_row, v_row = torch.zeros(P, device=dev), torch.zeros(P, device=dev)
+adam = engine.OptSpec("adam", 1e-2, 7, m_row, v_row)
+sgdm = engine.OptSpec("sgd", 1e-2, 7, m_row, None, momentum=0.9)
+t_adam = timeit("opt_step adam (opt_apply_cb_kernel)", lambda: engine.opt_step(theta, g, False, adam), n=1000)
+timeit("opt_step sgd momentum", lambda: engine.opt_step(theta, g, False, sgdm), n=1000)
+t_grad = timeit("fd_grad_fused zscore (again)", lambda: engine.fd_grad_fused(table, idx, rew, 0.0, 0, sign, n2, 2, 0.02, P,
+                                                                             out=g), n=1000)
+t_step = timeit("fd_step (any P)", lambda: engine.fd_step(table, idx, rew, 0.0, sign, n2, 2, 0.02, theta, 0.01, 0.5, g=g),
+                n=1000)
+t_opt = timeit("fd_step_opt adam", lambda: engine.fd_step_opt(table, idx, rew, 0.0, sign, n2, 2, 0.02, theta, adam, g=g),
+               n=1000)
+print("apply launch by difference: dsgd_apply_cb_kernel %.2f us, opt_apply_cb_kernel<ADAM> %.2f us (alone: %.2f us)"
+      % (t_step - t_grad, t_opt - t_grad, t_adam))

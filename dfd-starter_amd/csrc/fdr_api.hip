@@ -114,6 +114,8 @@ static int resolve(fdr_ctx* ctx, Context** out) {
   return FDR_OK;
 }
 
+int fdr::resolve_context(fdr_ctx* ctx, Context** out) { return resolve(ctx, out); }
+
 // The setters' context: no device check (unlike FDR_CTX) -- they touch host state only.
 static Context& ctx_or_default(fdr_ctx* ctx) { return ctx ? ctx->c : default_context(); }
 

@@ -26,6 +26,9 @@ struct Context {
 };
 Context& default_context();
 int context_cus(const Context& c);
+// The context of a call for an entry point outside fdr_api.hip: ctx's own, or the default one for NULL; FDR_ERR_INVALID
+// when ctx belongs to another device than the current one (what FDR_CTX does inside fdr_api.hip).
+int resolve_context(::fdr_ctx* ctx, Context** out);
 
 struct PolicyKey {
   int n_in, n_act;

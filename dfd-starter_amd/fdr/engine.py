@@ -762,6 +762,31 @@ def obs_stats_merge(mean, m2, count, acc_mean, acc_m2, acc_count):
                                   _stream(mean.device)), "fdr_obs_stats_merge")
 
 
+# ---- counter-based noise rows (utils/noise_sources.py CounterNoiseSource) --------------------------
+def noise_fill(seed, n_rows, n_params, row_stride=None, ids=None, first_id=0, out=None, device=None):
+    """out [n_rows * row_stride] f32: row r = the normals of direction id ids[r] (device int64 / uint64 bits, [n_rows])
+    or first_id + r under `seed` (fdr_noise_fill: Philox4x32-10 + Box-Muller, every element of the stride written)."""
+    _check_dev(ids, out)
+    n_rows, n_params = int(n_rows), int(n_params)
+    if row_stride is None:
+        row_stride = (n_params + 3) // 4 * 4
+    dev = out.device if out is not None else ids.device if ids is not None else \
+        torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if ids is not None and (ids.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or ids.numel() != n_rows
+                            or not ids.is_contiguous()):
+        raise ValueError("ids must be %d contiguous 64-bit integers" % n_rows)
+    if out is None:
+        out = torch.empty(n_rows * int(row_stride), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n_rows * int(row_stride):
+        raise ValueError("out must be contiguous float32 [n_rows * row_stride]")
+    if n_rows == 0:
+        return out
+    mask = (1 << 64) - 1
+    check(lib.fdr_noise_fill(_c(dev), int(seed) & mask, _p(ids), int(first_id) & mask, n_rows, n_params, int(row_stride),
+                             _p(out), _stream(dev)), "fdr_noise_fill")
+    return out
+
+
 # ---- delayed returns: lambda with policy drift (learner/finite_differences.py:66-114) -------------
 def fd_lambda_norms(table, idx, sign, slot, sigma, drift, n_params):
     """||fl32(sign * fl32(sigma * eps_i) + D[slot_i])||^2 per return (f64 [n])."""

@@ -39,6 +39,10 @@ Returns carry a current epoch in the synchronous engine; returns from an older e
 reference's async server mode) add the parameter drift theta_epoch - theta_now to lambda
 (finite_differences.py:66-92) -- fdr_fd_lambda_norms / fdr_fd_grad_lambda, single-process or sharded
 (a list of FDReturn on every rank: counts + rewards all-gathered, one all-reduce of g).
+
+With a CounterNoiseSource the table of every route above is the batch's own rows (FDBatch.noise_table, idx = row *
+row_stride); returns or batches that carry only their encoded direction ids have the distinct ids' rows filled again
+on the device (fdr_noise_fill with an ids array), bit for bit what the rollout gathered from.
 """
 import numpy as np
 import torch
@@ -47,7 +51,7 @@ from dsgd import DSGD
 from fdr import dist as fdist
 from fdr import engine
 from utils import math_helpers
-from utils.noise_sources import HostNoiseRows, is_host_noise, require_noise_source
+from utils.noise_sources import HostNoiseRows, is_counter_noise, is_host_noise, require_noise_source
 
 from .fd_return import FDBatch
 
@@ -124,6 +128,7 @@ class FiniteDifferences(object):
         require_noise_source(noise_source, "FiniteDifferences")
         self.noise_source = noise_source
         self._host_noise = is_host_noise(noise_source)
+        self._counter_noise = is_counter_noise(noise_source)
         self.omega = omega
         self.batch_size = batch_size
         self.process_group = process_group
@@ -169,13 +174,33 @@ class FiniteDifferences(object):
 
     # ------------------------------------------------------------------------------------------
     def _table(self, b=None):
-        """What lambda is gathered from: a host-noise batch's own fl32(noise) rows, else the shared table."""
+        """What lambda is gathered from: a host-noise or counter-noise batch's own rows, else the shared table.  A
+        counter-noise batch that arrives without its rows has them regenerated from its encoded ids."""
         t = getattr(b, "noise_table", None) if b is not None else None
         if t is not None:
             return t
+        if self._counter_noise:
+            if b is None or getattr(b, "encoded", None) is None:
+                raise ValueError("a counter noise source's FDBatch carries its rows (noise_table) or its ids (encoded)")
+            lpd = b.lanes_per_dir
+            table, idx = self._counter_rows(b.encoded[::lpd])
+            b.idx_host = np.repeat(idx, lpd)
+            b.idx = torch.as_tensor(b.idx_host, device=self.policy.flat.device)
+            b.noise_table = table
+            return table
         if self._host_noise:
             raise ValueError("a host noise source's FDBatch carries its noise rows (Worker.evaluate sets noise_table)")
         return self.noise_source.device_table(self.policy.flat.device)
+
+    def _counter_rows(self, encoded):
+        """Device rows of the directions a counter noise source encoded (ids as strings, any order, repeats allowed --
+        antithetic partners share one): -> (table [n_unique * row_stride], idx_host [len(encoded)] offsets into it).
+        One fdr_noise_fill over the distinct ids; bit for bit the rows the rollout gathered from."""
+        src = self.noise_source
+        ids = np.array([int(e) for e in encoded], dtype=np.uint64)
+        uniq, inv = np.unique(ids, return_inverse=True)
+        table = src.rows(uniq, len(uniq), self.policy.flat.device)
+        return table, inv.reshape(-1).astype(np.int64) * src.row_stride
 
     def _mix_coefs(self):
         """(1 - omega, omega, ent_coef) at this step (NSRA-ES; the reference's finite_differences.py:40-48)."""
@@ -435,14 +460,17 @@ class FiniteDifferences(object):
             # finite_differences.py:94: decode() regenerates each return's noise vector on the host (f64); the device
             # gathers lambda_i = sign fl32(sigma fl32(noise_i)) (+ drift) from those rows
             return self._step_returns_lambda(keep, policy_reward)
-        table = self.noise_source.device_table(dev)
         current = [r for r in keep if self.dist_map[r.epoch] is None]
         stale = [r for r in keep if self.dist_map[r.epoch] is not None]
         if stale:
             # finite_differences.py:88-114: lambda_i = sigma * eps_i + dist_map[epoch_i], v_i = lambda_i / ||lambda_i||^2
             return self._step_returns_lambda(keep, policy_reward)
         rewards = torch.as_tensor([r.reward for r in current], dtype=torch.float64, device=dev)
-        idx = np.array([int(r.encoded_noise) for r in current], dtype=np.int64)
+        if self._counter_noise:   # the encoded ids' rows, regenerated on the device; idx = row offsets into them
+            table, idx = self._counter_rows([r.encoded_noise for r in current])
+        else:
+            table = self.noise_source.device_table(dev)
+            idx = np.array([int(r.encoded_noise) for r in current], dtype=np.int64)
         sign = np.array([int(getattr(r, "sign", 1) or 1) for r in current], dtype=np.int8)
         idx_d = torch.as_tensor(idx, device=dev)
         sign_d = torch.as_tensor(sign, device=dev)
@@ -451,6 +479,8 @@ class FiniteDifferences(object):
         else:
             n2 = engine.fd_lambda_norms(table, idx_d, sign_d, None, self.noise_std, None, P)
         b = FDBatch(rewards, None, None, n2, idx_d, sign_d, idx, sign, self.epoch)
+        if self._counter_noise:
+            b.noise_table = table
         if self.objective == "mixed":
             b.novelty = torch.as_tensor([float(r.novelty) for r in current], dtype=torch.float64, device=dev)
             b.entropy = torch.as_tensor([float(r.entropy) for r in current], dtype=torch.float64, device=dev)
@@ -473,6 +503,8 @@ class FiniteDifferences(object):
             rows = HostNoiseRows(np.zeros(P, np.float32), noises, np.arange(n), np.ones(n, np.int8), self.noise_std,
                                  dev, with_theta=False)
             table, idx_host = rows.table, rows.idx_host
+        elif self._counter_noise:
+            table, idx_host = self._counter_rows([r.encoded_noise for r in keep])
         else:
             table = self.noise_source.device_table(dev)
             idx_host = np.array([int(r.encoded_noise) for r in keep], np.int64)

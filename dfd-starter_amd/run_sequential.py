@@ -38,7 +38,7 @@ from learner import FDBatch, FDState, FiniteDifferences
 from policies import AtariPolicy, DiscretePolicy, ImpalaPolicy, MujocoPolicy
 from strategy import StrategyHandler
 from utils import AdaptiveOmega, SharedNoiseTable, math_helpers
-from utils.noise_sources import RNGNoiseSource, SimpleNoiseSource
+from utils.noise_sources import CounterNoiseSource, RNGNoiseSource, SimpleNoiseSource
 from worker import Agent, Worker
 
 
@@ -150,7 +150,8 @@ class SequentialRunner(object):
             self.policy = MujocoPolicy(self.env.obs_dim, self.env.act_dim, seed=random_seed, device=self.device)
             dist_fn = math_helpers.gaussian_wasserstein_dist_from_strategies   # SURVEY finding 6 fixed
         opt = opt_fn(self.policy.parameters(), lr=learning_rate, **(opt_kwargs or {}))
-        # noise_source: "table" (SharedNoiseTable, the GPU fast path: offsets into an HBM-resident table) or the
+        # noise_source: "table" (SharedNoiseTable, the GPU fast path: offsets into an HBM-resident table), "counter"
+        # (CounterNoiseSource: the same path over fresh rows a kernel fills per step from direction ids) or the
         # reference runner's default "rng" (run_sequential.py:89, RNGNoiseSource) / "simple": host noise sources,
         # theta' rows materialised per lane (slow, correct; utils/noise_sources.py HostNoiseRows)
         if noise_source == "table":
@@ -158,8 +159,12 @@ class SequentialRunner(object):
         elif noise_source in ("rng", "simple"):
             cls = RNGNoiseSource if noise_source == "rng" else SimpleNoiseSource
             self.noise_source = cls(self.policy.num_params, random_seed=random_seed)
+        elif noise_source == "counter":
+            # fresh noise per direction made on the device (CounterNoiseSource: a kernel fills the step's rows from
+            # 64-bit direction ids); the fast path, like "table"
+            self.noise_source = CounterNoiseSource(self.policy.num_params, random_seed=random_seed, device=self.device)
         else:
-            raise ValueError("noise_source must be 'table', 'rng' or 'simple'")
+            raise ValueError("noise_source must be 'table', 'counter', 'rng' or 'simple'")
         self.strategy_handler = StrategyHandler(self.policy, dist_fn, max_history_size=max_strategy_history_size,
                                                 fp16=getattr(self.env, "fp16", False))
         self.agent = Agent(self.policy, self.env, random_seed, normalize_obs=normalize_obs)
@@ -273,14 +278,20 @@ class SequentialRunner(object):
             sign = np.concatenate([np.tile(np.array([1, -1], np.int8), n_dirs) if self.antithetic
                                    else np.ones(n_dirs, np.int8), np.zeros(int(is_eval.sum()), np.int8)])
             det = (sign == 0).astype(np.int8)
-            rows = None
-            if self.worker._host_noise:      # worker.py:27-28: one sample() per direction, theta' rows materialised
+            rows = noise_rows = None
+            if self.worker._host_noise:     # worker.py:27-28: one sample() per direction, theta' rows materialised
                 draws = [self.noise_source.sample() for _ in range(n_dirs)]
                 idx_dirs = [d[0] for d in draws]
                 noises = np.stack([d[1] for d in draws]) if n_dirs else np.zeros((0, self.policy.num_params))
                 row = np.concatenate([np.repeat(np.arange(n_dirs), lpd), np.zeros(int(is_eval.sum()), np.int64)])
                 res, idx_d, sign_d, rows = self.worker._launch_host(noises, row, sign, det, jiggle=False)
                 lidx = rows.idx_host
+            elif self.worker._counter_noise:   # ids n .. n + n_dirs - 1: their rows filled on the device, the fast path
+                idx_dirs = self.noise_source.sample_ids(n_dirs)
+                noise_rows = self.worker._counter_rows(idx_dirs[0] if n_dirs else 0, n_dirs)
+                lidx = np.concatenate([np.repeat(np.arange(n_dirs, dtype=np.int64) * self.noise_source.row_stride, lpd),
+                                       np.zeros(int(is_eval.sum()), np.int64)])
+                res, idx_d, sign_d = self.worker.launch(lidx, sign, det, jiggle=False, table=noise_rows)
             else:
                 idx_dirs = self.noise_source.sample_batch(n_dirs)
                 # lane layout: training lanes first (lanes of a direction contiguous), eval lanes last
@@ -290,7 +301,9 @@ class SequentialRunner(object):
             lidx, sign = np.repeat(lidx, E), np.repeat(sign, E)
             if self.global_obs is not None and getattr(res, "obs_mean", None) is not None:
                 engine.obs_stats_merge(res.obs_mean, res.obs_m2, res.obs_count, *self.global_obs)
-            nov_d = self.worker.lane_novelty(idx_d, sign_d, table=None if rows is None else rows.table)  # worker.py:53
+            if rows is not None:
+                noise_rows = rows.table
+            nov_d = self.worker.lane_novelty(idx_d, sign_d, table=noise_rows)  # worker.py:53
             nov = np.zeros(len(lidx)) if nov_d is None else nov_d.cpu().numpy()
             rew = res.reward.cpu().numpy() + np.array([self.agent.rng.choice((-1e-12, 1e-12)) for _ in lidx])
             ent = res.entropy.cpu().numpy()
@@ -314,8 +327,8 @@ class SequentialRunner(object):
                             res.timesteps[:n_train], res.norm2[:n_train], idx_d[:n_train], sign_d[:n_train],
                             lidx[:n_train], sign[:n_train], self.learner.epoch, lanes_per_dir=lpd * E,
                             novelty=None if nov_d is None else nov_d[:n_train])   # the device tensor: no host trip
-            if rows is not None:
-                batch.noise_table = rows.table
+            if noise_rows is not None:
+                batch.noise_table = noise_rows
             update_magnitude = self.learner.step(batch, self.policy_reward, self.policy_novelty, self.policy_entropy)
             if self.vbn_buffer is not None:
                 self.policy.compute_vbn(self.vbn_buffer)

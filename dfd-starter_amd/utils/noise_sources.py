@@ -10,6 +10,10 @@
   * ``peek_batch(n)`` draws ahead without consuming: the next sample / sample_batch calls return those
     indices first, so the stream is unchanged (a batch of n draws is n single draws) -- the worker uses it
     to upload the next FD step's lane descriptors while the current rollout runs.
+
+``CounterNoiseSource`` (build extension) keeps that path and drops the table: every direction is a fresh vector a
+kernel regenerates from a 64-bit id (Philox4x32-10 + Box-Muller, fdr_noise_fill) -- RNGNoiseSource's statistics at
+the table path's cost.  ``RNGNoiseSource`` / ``SimpleNoiseSource`` are the reference's host sources, slow by design.
 """
 import ctypes
 
@@ -158,25 +162,101 @@ class SimpleNoiseSource(object):
         return noise
 
 
+class CounterNoiseSource(object):
+    """Fresh noise made on the device (build extension: the statistics of RNGNoiseSource -- an independent vector per
+    perturbation -- not its PCG64 stream).  Direction id d (a 64-bit counter) under seed s IS the vector: element quad j
+    is one Philox4x32-10 block of (j, d, s) turned into four normals by Box-Muller (fdr_noise_fill), so a
+    perturbation is encoded as the integer d and any rank, or the learner an epoch later, regenerates it alone.
+
+    Neither a device table nor a host source: a step's rows are one device buffer [n * row_stride] f32 filled by one
+    kernel, handed to the rollout / learner / novelty kernels as "the table" with idx = row * row_stride -- the fast
+    path (theta' = fl32(theta +- fl32(sigma eps)) formed in the kernels); nothing crosses PCIe but lane descriptors.
+      row_stride      n_params rounded up to a multiple of 4 (a row starts on a 16-byte boundary)
+      next_id         the direction counter; sample_ids(n) returns the next n ids and advances it, peek_ids(n) does not
+      rows(ids, n)    a FRESH device buffer of n rows (torch's allocator, current stream): ids = the first id (rows
+                      are first, first + 1, ...) or n explicit ids in any order; a batch that holds its rows stays valid
+                      while later steps fill their own
+      sample/decode   the reference interface: (str(id), f64 copy of the row) / the row of an encoded id, regenerated
+                      on the device -- bit for bit the f32 values the kernels used
+    A buffer above max_bytes is refused (ValueError) before anything is allocated."""
+
+    counter_noise = True
+
+    def __init__(self, n_params, random_seed=123, device=None, max_bytes=8 << 30):
+        self.n_params = int(n_params)
+        if self.n_params < 1:
+            raise ValueError("n_params must be >= 1")
+        self.seed = int(random_seed) & 0xFFFFFFFFFFFFFFFF
+        self.device = None if device is None else torch.device(device)
+        self.row_stride = (self.n_params + 3) // 4 * 4
+        self.max_bytes = int(max_bytes)
+        self.next_id = 0
+
+    def peek_ids(self, n):
+        return np.arange(self.next_id, self.next_id + int(n), dtype=np.uint64)
+
+    def sample_ids(self, n):
+        ids = self.peek_ids(n)
+        self.next_id += int(n)
+        return ids
+
+    def rows(self, ids_or_first, n, device=None):
+        n = int(n)
+        nbytes = n * self.row_stride * 4
+        if nbytes > self.max_bytes:
+            raise ValueError("CounterNoiseSource: %d rows of %d parameters need %d bytes, above max_bytes = %d"
+                             % (n, self.n_params, nbytes, self.max_bytes))
+        from fdr import engine
+        dev = torch.device(device) if device is not None else self.device if self.device is not None else \
+            torch.device("cuda", torch.cuda.current_device())
+        if np.ndim(ids_or_first) == 0:
+            return engine.noise_fill(self.seed, n, self.n_params, self.row_stride, first_id=int(ids_or_first), device=dev)
+        ids = np.ascontiguousarray(np.asarray(ids_or_first, dtype=np.uint64))
+        if ids.shape != (n,):
+            raise ValueError("rows(): %d ids given for %d rows" % (ids.size, n))
+        ids_d = torch.from_numpy(ids.view(np.int64)).to(dev)    # the same 64 bits: torch's uint64 support is partial
+        return engine.noise_fill(self.seed, n, self.n_params, self.row_stride, ids=ids_d, device=dev)
+
+    def sample(self):
+        d = int(self.sample_ids(1)[0])
+        enc = "{}".format(d)
+        return enc, self.decode(enc)
+
+    def decode(self, enc):
+        return self.rows(int(enc), 1)[:self.n_params].cpu().numpy().astype(np.float64)
+
+
+def is_counter_noise(noise_source):
+    """A counter-based source (CounterNoiseSource): rows(ids, n) fills device rows from direction ids."""
+    return bool(getattr(noise_source, "counter_noise", False)) and hasattr(noise_source, "rows")
+
+
 def is_device_table(noise_source):
     """A table source the kernels gather from by offset (SharedNoiseTable's device_table / sample_batch interface)."""
+    if is_counter_noise(noise_source):
+        return False
     return hasattr(noise_source, "device_table") and hasattr(noise_source, "sample_batch")
 
 
 def is_host_noise(noise_source):
     """A host source with the reference interface sample() -> (encoded, noise) / decode(encoded) -> noise."""
+    if is_counter_noise(noise_source):
+        return False
     return (not is_device_table(noise_source) and hasattr(noise_source, "sample") and
             hasattr(noise_source, "decode"))
 
 
 def require_noise_source(noise_source, who):
     """Worker / FiniteDifferences take a SharedNoiseTable (the fast path: offsets into an HBM-resident table, theta'
-    never materialised) or a host source with the reference's sample / decode interface (RNGNoiseSource,
-    SimpleNoiseSource: theta' rows materialised per lane).  Anything else is refused at construction with a clear
-    error rather than an AttributeError in the middle of a step."""
+    never materialised), a CounterNoiseSource (the same fast path over rows a kernel fills per step) or a host source
+    with the reference's sample / decode interface (RNGNoiseSource, SimpleNoiseSource: theta' rows materialised per
+    lane).  Anything else is refused at construction with a clear error rather than an AttributeError in the middle of
+    a step."""
+    if is_counter_noise(noise_source):
+        return
     if not (is_device_table(noise_source) or is_host_noise(noise_source)):
-        raise TypeError("%s needs a noise source with the reference interface (SharedNoiseTable, RNGNoiseSource or "
-                        "SimpleNoiseSource); got %s" % (who, type(noise_source).__name__))
+        raise TypeError("%s needs a noise source with the reference interface (SharedNoiseTable, CounterNoiseSource, "
+                        "RNGNoiseSource or SimpleNoiseSource); got %s" % (who, type(noise_source).__name__))
 
 
 class HostNoiseRows(object):

@@ -5,6 +5,8 @@ the noise-table indices on the host in the reference's order (utils/noise_source
 them to the device and runs every (perturbation x env) lane for a whole episode in ONE
 fdr_rollout launch.  theta' = theta + sign * fl32(sigma * eps) is formed inside the kernel
 (bit-exact with worker.py:28) and never materialised.  The result is an FDBatch (device SoA).
+With a CounterNoiseSource the draw is a range of direction ids and one fdr_noise_fill launch that fills this rank's
+rows on the device; the same rollout then reads them as its table (idx = row * row_stride).
 
 ``collect_returns(n)`` keeps the reference's list-of-FDReturn API: the eval coin flips
 (worker.py:23) and index draws happen in the reference's order, then all n episodes run in one
@@ -18,7 +20,7 @@ import torch
 from fdr import engine
 from learner.fd_return import FDBatch
 from utils.math_helpers import WelfordRunningStat
-from utils.noise_sources import HostNoiseRows, is_host_noise, require_noise_source
+from utils.noise_sources import HostNoiseRows, is_counter_noise, is_host_noise, require_noise_source
 
 
 def obs_partials(res):
@@ -34,6 +36,7 @@ class Worker(object):
         require_noise_source(noise_source, "Worker")
         self.noise_source = noise_source
         self._host_noise = is_host_noise(noise_source)   # RNGNoiseSource / SimpleNoiseSource: theta' rows per lane
+        self._counter_noise = is_counter_noise(noise_source)   # CounterNoiseSource: the step's rows filled on the device
         self.strategy_handler = strategy_handler
         self.sigma = sigma
         self.epoch = -1
@@ -117,12 +120,13 @@ class Worker(object):
         return (arrs, ev) if defer_wait else arrs
 
     def launch(self, idx, sign, det, seed=None, out=None, jiggle=True, lane_offset=0, lanes_dev=None, pairs=False,
-               timing=None, rows=None):
+               timing=None, rows=None, table=None):
         """Run one rollout over explicit lanes (host arrays) -> FDBatch (asynchronous).  lanes_dev: the same lanes
         already on the device (idx, sign, det), e.g. uploaded ahead by evaluate(prefetch=True).  pairs: lanes 2p,
         2p+1 are antithetic pairs (checked here) -- an Impala rollout then streams each pair's sigma-eps once
         (fdr_impala_desc.pairs).  timing: a (start, end) pair of torch.cuda.Event recorded on the stream right
-        around the rollout launch(es), nothing else inside (bench.py's kernel-time pass)."""
+        around the rollout launch(es), nothing else inside (bench.py's kernel-time pass).  table: the noise rows idx
+        points into, in place of the source's shared table (a CounterNoiseSource's rows of this launch)."""
         p = self.policy
         n = len(idx)
         idx_d, sign_d, det_d = lanes_dev if lanes_dev is not None else self._lanes_to_device(idx, sign, det)
@@ -132,7 +136,8 @@ class Worker(object):
             lanes = engine.lanes_desc(rows.theta, p.num_params, None, idx_d, sign_d, self.sigma, det_d, lane_offset)
             pairs = False
         else:
-            table = self.noise_source.device_table(p.flat.device)
+            if table is None:
+                table = self.noise_source.device_table(p.flat.device)
             lanes = engine.lanes_desc(p.flat, 0, table, idx_d, sign_d, self.sigma, det_d, lane_offset)
         bm, bv = p.bn_stats()
         if seed is None:
@@ -242,6 +247,8 @@ class Worker(object):
         timing: (start, end) events around the rollout launch (Worker.launch)."""
         if self._host_noise:
             return self._evaluate_host(n_dirs, antithetic, seed, lane_range, out, novelty, timing)
+        if self._counter_noise:   # prefetch has nothing to do: the lane descriptors are constants of the call shape
+            return self._evaluate_counter(n_dirs, antithetic, seed, lane_range, out, novelty, timing)
         pre, self._next = self._next, None
         idx = self.noise_source.sample_batch(n_dirs)
         lidx, sign, det, lane_range, rank_lanes = self._lanes_of(idx, n_dirs, antithetic, lane_range)
@@ -310,6 +317,59 @@ class Worker(object):
         b.rank_lanes = None if rank_lanes is None else [k * E for k in rank_lanes]
         return b
 
+    def _counter_rows(self, first_id, n):
+        """The device rows of n directions first_id, first_id + 1, ... (one fdr_noise_fill); one zero row when there is
+        none, so that eval-only launches still have a table to point at."""
+        src = self.noise_source
+        dev = self.policy.flat.device
+        if n == 0:
+            return torch.zeros(src.row_stride, dtype=torch.float32, device=dev)
+        return src.rows(int(first_id), n, dev)
+
+    def _evaluate_counter(self, n_dirs, antithetic, seed, lane_range, out, novelty, timing):
+        """evaluate() with a CounterNoiseSource: every rank advances the counter by n_dirs and fills the rows of its own
+        directions only (ids are contiguous: first id + row); lane l gathers at idx = local_row * row_stride, the fast
+        path with antithetic pairs.  The descriptors depend on the call's shape alone: uploaded once."""
+        src = self.noise_source
+        ids = src.sample_ids(n_dirs)
+        _, sign, det, lane_range, rank_lanes = self._lanes_of(np.zeros(int(n_dirs), np.int64), n_dirs, antithetic,
+                                                              lane_range)
+        lpd = 2 if antithetic else 1
+        lo = 0 if lane_range is None else lane_range[0]
+        d_lo = lo // lpd
+        nd = len(sign) // lpd
+        world, rank = (1, 0)
+        if lane_range is not None:
+            from fdr import dist as fdist
+            world, rank = fdist.world_rank()
+        ckey = ("counter", int(n_dirs), bool(antithetic), None if lane_range is None else tuple(lane_range), world, rank)
+        c = self._lane_consts.get(ckey)
+        if c is None:
+            dev = self.policy.flat.device
+            lidx = np.repeat(np.arange(nd, dtype=np.int64) * src.row_stride, lpd)
+            up = tuple(torch.from_numpy(np.array(a)).to(dev) for a in (lidx, sign, det))   # copies: read-only arrays
+            lidx.setflags(write=False)
+            c = self._lane_consts[ckey] = (lidx, up)
+        lidx, lanes_dev = c
+        rows = self._counter_rows(ids[d_lo] if nd else 0, nd)
+        res, idx_d, sign_d = self.launch(lidx, sign, det, seed=seed, out=out, lane_offset=lo, lanes_dev=lanes_dev,
+                                         pairs=antithetic, timing=timing, table=rows)
+        E = getattr(self.agent.env, "envs_per_lane", 1)
+        enc = [e for e in map(str, ids[d_lo:d_lo + nd].tolist()) for _ in range(lpd * E)]
+        if E > 1:
+            lidx, sign = np.repeat(lidx, E), np.repeat(sign, E)
+        if getattr(self.agent.env, "terminates", False):
+            self.agent.add_timesteps(res.timesteps)
+        else:
+            self.agent.cumulative_timesteps += int(len(lidx)) * self.agent.env.episode_len
+        nov = self.lane_novelty(idx_d, sign_d, table=rows) if novelty else None
+        b = FDBatch(res.reward, res.entropy, res.timesteps, res.norm2, idx_d, sign_d, lidx, sign, self.epoch,
+                    lanes_per_dir=lpd * E, novelty=nov)
+        b.noise_table, b.encoded = rows, enc
+        b.obs_stats = obs_partials(res)
+        b.rank_lanes = None if rank_lanes is None else [k * E for k in rank_lanes]
+        return b
+
     # ---- reference API ----------------------------------------------------------------------
     @torch.no_grad()
     def collect_returns(self, n=1):
@@ -317,7 +377,7 @@ class Worker(object):
         idx = np.zeros(n, np.int64)
         k = int((~is_eval).sum())
         sign = np.where(is_eval, 0, 1).astype(np.int8)
-        host_rows, enc = None, None
+        host_rows, enc, table = None, None, None
         if self._host_noise:        # worker.py:27-28 per training lane: sample() in order, theta' materialised
             draws = [self.noise_source.sample() for _ in range(k)]
             row = np.cumsum(~is_eval) - 1
@@ -327,11 +387,18 @@ class Worker(object):
             idx = host_rows.idx_host
             it = iter(draws)
             enc = ["0" if e else next(it)[0] for e in is_eval]
+        elif self._counter_noise:   # one id per training lane, in order; its row filled on the device
+            ids = self.noise_source.sample_ids(k)
+            table = self._counter_rows(ids[0] if k else 0, k)
+            idx[~is_eval] = np.arange(k, dtype=np.int64) * self.noise_source.row_stride
+            res, idx_d, sign_d = self.launch(idx, sign, is_eval.astype(np.int8), jiggle=False, table=table)
+            it = iter(ids)
+            enc = ["0" if e else str(int(next(it))) for e in is_eval]
         else:
             if k:
                 idx[~is_eval] = self.noise_source.sample_batch(k)
             res, idx_d, sign_d = self.launch(idx, sign, is_eval.astype(np.int8), jiggle=False)
-        nov = self.lane_novelty(idx_d, sign_d, table=None if host_rows is None else host_rows.table)
+        nov = self.lane_novelty(idx_d, sign_d, table=table if host_rows is None else host_rows.table)
         E = getattr(self.agent.env, "envs_per_lane", 1)
         if E > 1:
             idx, sign, is_eval = np.repeat(idx, E), np.repeat(sign, E), np.repeat(is_eval, E)
@@ -342,7 +409,7 @@ class Worker(object):
                     is_eval=is_eval)
         if enc is not None:
             b.encoded = [e for e in enc for _ in range(E)] if E > 1 else enc
-            b.noise_table = host_rows.table
+            b.noise_table = table if host_rows is None else host_rows.table
         b.novelty = None if nov is None else nov.cpu().numpy()
         b.obs_stats = obs_partials(res)
         rets = b.to_returns()
@@ -366,7 +433,7 @@ class Worker(object):
         E = getattr(self.agent.env, "envs_per_lane", 1)
         if E > 1:
             idx_d, sign_d = idx_d[::E].contiguous(), sign_d[::E].contiguous()
-        if table is None:      # the shared table; a host noise source passes its launch's rows (HostNoiseRows)
+        if table is None:      # the shared table; a host / counter noise source passes its launch's rows
             table = self.noise_source.device_table(self.policy.flat.device)
         nov = h.lane_novelty(table, idx_d, sign_d, self.sigma, pairs=self._launch_pairs)
         return nov.repeat_interleave(E) if E > 1 else nov

@@ -115,7 +115,8 @@ typedef struct fdr_lanes_desc {
  * the ctx's device (FDR_ERR_INVALID otherwise).  A ctx is not shared across threads without external locking; two
  * contexts -- on one device or on two -- are independent.  ctx = NULL selects the process-wide default context
  * (device-agnostic; FDR_ROLLOUT in the environment sets its initial rollout selection, and new contexts copy it). */
-const char* fdr_version(void); /* "fdr 0.5 gfx950" (0.5: fdr_impala_bn_refresh, fdr_atari_bn_refresh, fdr_atari_strategies; 0.4:
+const char* fdr_version(void); /* "fdr 0.5 gfx950" (0.5: fdr_impala_bn_refresh, fdr_atari_bn_refresh, fdr_atari_strategies,
+                                  fdr_noise_fill; 0.4:
                                   fdr_env_desc.done_threshold / done_dim) */
 const char* fdr_last_error(void);
 typedef struct fdr_ctx fdr_ctx;
@@ -220,6 +221,22 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
  * the smallest all-ones mask >= max_idx - 1, rejected while > max_idx - 1 (numpy's legacy masked path).  HOST
  * pointers, no device work; FDR_ERR_UNSUPPORTED when max_idx - 1 needs more than 32 bits. */
 int fdr_noise_draw_indices(uint32_t* key, int32_t* pos, int64_t max_idx, int32_t n, int64_t* out);
+
+/* ---- counter-based noise rows (added within fdr 0.5: one export, no struct) -----------------------
+ * Fills out [n_rows * row_stride] f32 (device) with standard normals that are a pure function of (seed, row id,
+ * element): row r, at r * row_stride, belongs to direction id ids[r] (device [n_rows]) or, with ids == NULL,
+ * first_id + r.  Element quad j of a row (elements 4j .. 4j+3) is one Philox4x32-10 block, counter
+ * (j, id & 0xffffffff, id >> 32, 0), key (seed & 0xffffffff, seed >> 32), Random123's constants; its words x0..x3
+ * become four normals by two Box-Muller pairs (x0, x1), (x2, x3): for (a, b), u1 = ((a >> 8) + 1) 2^-24,
+ * u2 = (b >> 8) 2^-24, r = sqrtf(-2 logf(u1)), z = (r cospif(2 u2), r sinpif(2 u2))  (DESIGN.md 5).
+ * row_stride is a multiple of 4, at least n_params rounded up to 4, and out is 16-byte aligned (FDR_ERR_INVALID
+ * otherwise).  EVERY element of a row's stride is written: those from n_params to row_stride continue the row's
+ * stream, so a row's values do not depend on row_stride.  With idx = r * row_stride the buffer serves every
+ * kernel here as a noise table (fdr_lanes_desc.table, fdr_fd_grad*, fdr_fd_lambda_norms, ...).
+ * Asynchronous on stream, allocates nothing, capturable.  out NULL, n_rows < 0 or n_params < 1: FDR_ERR_INVALID;
+ * n_rows == 0: FDR_OK, no launch; row_stride above 2^33: FDR_ERR_UNSUPPORTED. */
+int fdr_noise_fill(fdr_ctx* ctx, uint64_t seed, const uint64_t* ids, uint64_t first_id, int64_t n_rows,
+                   int32_t n_params, int64_t row_stride, float* out, fdr_stream stream);
 
 /* ---- obs statistics merge (utils/math_helpers.py:68-87, increment_from_obs_stats_update) --------
  * Folds n partial Welford statistics (mean/m2 [n, dim] f32, count [n] i32, e.g. from

@@ -106,6 +106,15 @@ struct RolloutArgs {
   // NULL, or [n_lanes, T, k] host-injected draws replacing the counter stream (fdr_rollout_extras.u_inject)
   const float* u_inject;
 };
+// fdr_rollout_episodes' kernel argument: the rollout's own (synthetic / trap members, states and u_inject unused) and
+// the episode loop's.  A struct of its own: a member added to RolloutArgs moves the hidden kernel arguments behind it,
+// which changes an s_load offset in every kernel that takes RolloutArgs (tools/isa_diff.py).
+struct EpisodesArgs {
+  RolloutArgs r;
+  int n_episodes;              // K: episodes per lane
+  const int64_t* episode_ids;  // NULL, or [n_lanes, K] stream ids
+  double* ret_sq;              // NULL, or [n_lanes] sum of squared episode returns
+};
 
 int launch_policy_forward(const Context& ctx, const PolicyKey& k, const LanesArgs& lanes, int n_lanes,
                           const float* bn_mean, const float* bn_var, const float* x, float* out0,
@@ -140,6 +149,9 @@ inline bool physics_policy_ok(const PhysicsEnv& e, const PolicyKey& k) {
 }
 // trap gridworld and the physics envs
 int launch_rollout_env(const PolicyKey& k, int env_kind, const RolloutArgs& args, hipStream_t stream);
+// the physics envs, args.n_episodes episodes per lane in one launch (fdr_rollout_episodes.hip); any other env kind or
+// a policy that is not the env's own: FDR_ERR_UNSUPPORTED, nothing launched
+int launch_rollout_episodes(const PolicyKey& k, int env_kind, const EpisodesArgs& args, hipStream_t stream);
 // two lanes per wave; round_lanes: lanes of one resident round (more go out as consecutive launches)
 int launch_rollout_pair(const PolicyKey& k, const RolloutArgs& args, int round_lanes, hipStream_t stream);
 // fdr_diag_theta_prime: what MlpLane::load / MlpPair::load / DynLane::load read through a RecordSrc (out / reads /

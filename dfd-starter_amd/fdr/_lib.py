@@ -40,7 +40,8 @@ EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy",
            "fdr_impala_bn_refresh_workspace_bytes", "fdr_impala_bn_refresh", "fdr_atari_strategies_workspace_bytes",
            "fdr_atari_strategies", "fdr_atari_bn_refresh_workspace_bytes", "fdr_atari_bn_refresh",
            "fdr_diag_theta_prime", "fdr_fd_grad_fused_mix", "fdr_fd_step_mix", "fdr_fd_weights_mix",
-           "fdr_opt_workspace_bytes", "fdr_opt_step", "fdr_fd_step_opt", "fdr_fd_step_mix_opt", "fdr_noise_fill")
+           "fdr_opt_workspace_bytes", "fdr_opt_step", "fdr_fd_step_opt", "fdr_fd_step_mix_opt", "fdr_noise_fill",
+           "fdr_rollout_episodes")
 
 
 class FDRError(RuntimeError):
@@ -109,6 +110,9 @@ def _load():
         "fdr_rollout_ex": (ctypes.c_int, [P, ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc),
                                           ctypes.POINTER(LanesDesc), I32, U64, I32, P, P, P, P, P, P,
                                           ctypes.POINTER(RolloutExtras), P]),
+        "fdr_rollout_episodes": (ctypes.c_int, [P, ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc),
+                                                ctypes.POINTER(LanesDesc), I32, U64, I32, P, P, I32, P, P, P, P, P, P,
+                                                P, P, P, F32, P]),
         "fdr_obs_stats_merge": (ctypes.c_int, [P, P, P, P, I32, I32, P, P, P, P]),
         "fdr_noise_draw_indices": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_int32), I64, I32, P]),
         "fdr_noise_fill": (ctypes.c_int, [P, U64, P, U64, I64, I32, I64, P, P]),

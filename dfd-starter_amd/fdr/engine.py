@@ -238,6 +238,47 @@ def rollout(spec, env, lanes, n_lanes, seed, jiggle=True, obs_mean=None, obs_std
     return out
 
 
+def rollout_episodes(spec, env, lanes, n_lanes, seed, n_episodes, episode_ids=None, jiggle=True, obs_mean=None,
+                     obs_std=None, bn_mean=None, bn_var=None, obs_stats=None, ret_sq=False, out=None, device=None,
+                     ctx=None):
+    """fdr_rollout_episodes: n_episodes episodes per lane in one launch (the physics envs), theta' formed once per
+    lane.  episode_ids: None (episode e of lane l draws as global lane (lane_offset + l) * K + e) or an int64
+    [n_lanes, n_episodes] device tensor of stream ids in [0, 2^32) -- lanes given equal ids share their resets and
+    draws.  -> RolloutResult: reward = the mean episode return, timesteps = the summed steps, entropy over all
+    visited states; .reward_sq (sum of squared episode returns) with ret_sq=True; obs_stats as rollout()."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    _check_dev(obs_mean, obs_std, bn_mean, bn_var, episode_ids)
+    K = int(n_episodes)
+    if episode_ids is not None:
+        if episode_ids.dtype != torch.int64 or not episode_ids.is_contiguous() or \
+                episode_ids.numel() != n_lanes * K:
+            raise ValueError("episode_ids must be contiguous int64 [n_lanes, n_episodes]")
+    if out is None:
+        buf = torch.empty(28 * n_lanes, dtype=torch.uint8, device=dev)
+        out = RolloutResult(buf[:8 * n_lanes].view(torch.float64), buf[8 * n_lanes:16 * n_lanes].view(torch.float64),
+                            buf[24 * n_lanes:].view(torch.int32), buf[16 * n_lanes:24 * n_lanes].view(torch.float64))
+    sq = None
+    if ret_sq:
+        sq = getattr(out, "reward_sq", None)
+        if sq is None:
+            sq = out.reward_sq = torch.empty(n_lanes, dtype=torch.float64, device=dev)
+    om = m2 = cnt = None
+    chance = 0.0
+    if obs_stats is not None:
+        chance = float(obs_stats)
+        om = out.obs_mean = torch.empty((n_lanes, spec.n_in), dtype=torch.float32, device=dev)
+        m2 = out.obs_m2 = torch.empty_like(om)
+        cnt = out.obs_count = torch.empty(n_lanes, dtype=torch.int32, device=dev)
+    pd = spec.desc(bn_mean, bn_var)
+    ed = env.desc()
+    check(lib.fdr_rollout_episodes(_c(dev, ctx), ctypes.byref(pd), ctypes.byref(ed), ctypes.byref(lanes), n_lanes,
+                                   ctypes.c_uint64(seed & ((1 << 64) - 1)), 1 if jiggle else 0, _p(obs_mean),
+                                   _p(obs_std), K, _p(episode_ids), _p(out.reward), _p(sq), _p(out.entropy),
+                                   _p(out.timesteps), _p(out.norm2), _p(om), _p(m2), _p(cnt), chance, _stream(dev)),
+          "fdr_rollout_episodes")
+    return out
+
+
 def fd_weights(rewards_all, policy_reward, lane_lo, sign_local, norm2_local, lanes_per_dir, sigma, coef=None):
     _check_dev(rewards_all, sign_local, norm2_local)
     n_local = sign_local.numel()

@@ -106,8 +106,12 @@ class SequentialRunner(object):
                  log_to_wandb=False, wandb_project="fd-starter", wandb_group=None, wandb_run_name=None,
                  noise_table_size=25_000_000, antithetic=False, episode_len=None, device=None, verbose=True,
                  envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False, env_shape=None,
-                 objective="reward", opt_kwargs=None):
-        """opt_fn: DSGD (the reference runner's), or any torch.optim class -- opt_fn(policy.parameters(),
+                 objective="reward", opt_kwargs=None, episodes_per_lane=1, common_random_numbers=False):
+        """episodes_per_lane = K, common_random_numbers = False | True ("pair") | "pair" | "batch": evaluation-noise
+        controls of the physics envs (Worker): every lane -- eval lanes too -- returns the mean of K episodes run in
+        one launch, and the +eps / -eps lanes of a direction ("pair") or all lanes ("batch") share resets and draws.
+        The learner still receives one return per lane.
+        opt_fn: DSGD (the reference runner's), or any torch.optim class -- opt_fn(policy.parameters(),
         lr=learning_rate, **opt_kwargs); torch.optim.Adam / AdamW / SGD step inside the learner's apply launch, any
         other optimizer through the learner's generic route (FiniteDifferences).
         env_shape = (obs_dim, act_dim, discrete): instead of the env_id mapping, a SyntheticEnv of that shape
@@ -169,7 +173,10 @@ class SequentialRunner(object):
                                                 fp16=getattr(self.env, "fp16", False))
         self.agent = Agent(self.policy, self.env, random_seed, normalize_obs=normalize_obs)
         self.worker = Worker(self.policy, self.agent, self.noise_source, self.strategy_handler, sigma=noise_std,
-                             random_seed=random_seed, eval_prob=eval_prob)
+                             random_seed=random_seed, eval_prob=eval_prob, episodes_per_lane=episodes_per_lane,
+                             common_random_numbers=common_random_numbers)
+        self.episodes_per_lane = self.worker.episodes_per_lane
+        self.worker.want_ret_sq = self.episodes_per_lane > 1   # the within-lane spread of the epoch report
         self.learner = FiniteDifferences(self.policy, opt, self.omega, self.noise_source, noise_std=noise_std,
                                          batch_size=batch_size, ent_coef=ent_coef,
                                          max_delayed_return=max_delayed_return, objective=objective)
@@ -291,12 +298,13 @@ class SequentialRunner(object):
                 noise_rows = self.worker._counter_rows(idx_dirs[0] if n_dirs else 0, n_dirs)
                 lidx = np.concatenate([np.repeat(np.arange(n_dirs, dtype=np.int64) * self.noise_source.row_stride, lpd),
                                        np.zeros(int(is_eval.sum()), np.int64)])
-                res, idx_d, sign_d = self.worker.launch(lidx, sign, det, jiggle=False, table=noise_rows)
+                res, idx_d, sign_d = self.worker.launch(lidx, sign, det, jiggle=False, table=noise_rows,
+                                                        lanes_per_dir=lpd)
             else:
                 idx_dirs = self.noise_source.sample_batch(n_dirs)
                 # lane layout: training lanes first (lanes of a direction contiguous), eval lanes last
                 lidx = np.concatenate([np.repeat(idx_dirs, lpd), np.zeros(int(is_eval.sum()), np.int64)])
-                res, idx_d, sign_d = self.worker.launch(lidx, sign, det, jiggle=False)
+                res, idx_d, sign_d = self.worker.launch(lidx, sign, det, jiggle=False, lanes_per_dir=lpd)
             # E envs per lane (frame envs): one return per (lane, env), lane-major; idx_d / sign_d repeat per env
             lidx, sign = np.repeat(lidx, E), np.repeat(sign, E)
             if self.global_obs is not None and getattr(res, "obs_mean", None) is not None:
@@ -352,6 +360,11 @@ class SequentialRunner(object):
                           "Noisy Novelty": float(np.mean(nov[:n_train])),
                           "Update Magnitude": update_magnitude,
                           "Omega": self.omega.omega}
+                if self.episodes_per_lane > 1:
+                    # the spread of a training lane's K episode returns about its mean: sqrt(mean_l(ret_sq / K - mean^2))
+                    K = self.episodes_per_lane
+                    var = res.reward_sq[:n_train].cpu().numpy() / K - res.reward[:n_train].cpu().numpy() ** 2
+                    report["Noisy Reward Within-Lane Std"] = float(np.sqrt(max(float(np.mean(var)), 0.0)))
                 entry = dict(report, idx=idx_dirs, rewards=rew[:n_train])
                 if self.objective == "mixed":   # what the step weighted: the training lanes' other two channels
                     entry.update(novelties=np.asarray(nov[:n_train], np.float64), entropies=np.asarray(

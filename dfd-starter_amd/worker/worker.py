@@ -29,8 +29,52 @@ def obs_partials(res):
     return None if m is None else (res.obs_mean, res.obs_m2, res.obs_count)
 
 
+CRN_MODES = (False, "pair", "batch")
+
+
+def crn_mode(value):
+    """common_random_numbers as given -> False | "pair" | "batch" (True means "pair")."""
+    mode = "pair" if value is True else (False if value is None else value)
+    if mode not in CRN_MODES:
+        raise ValueError("common_random_numbers must be False, True, 'pair' or 'batch' (got %r)" % (value,))
+    return mode
+
+
+def episode_stream_ids(mode, sign, lane_offset, n_episodes, lanes_per_dir=1):
+    """The random-stream ids of one fdr_rollout_episodes launch, from host arrays (pure: no GPU): int64
+    [n_lanes, n_episodes], or None for mode False (the kernel's default, (g) K + e with g = lane_offset + l).
+      "pair"   the lanes of a direction (lanes_per_dir consecutive global lanes) share the streams of its first lane:
+               (g - g % lanes_per_dir) K + e; a sign-0 (eval) lane keeps its own, g K + e
+      "batch"  every lane plays the same K streams: e
+    Ids are functions of the global lane alone, so a shard of whole directions draws what the whole launch draws;
+    lane_offset must therefore be a multiple of lanes_per_dir.  Ids fill the counter's 32-bit lane field."""
+    mode = crn_mode(mode)
+    K, lpd = int(n_episodes), int(lanes_per_dir)
+    if K < 1 or lpd < 1:
+        raise ValueError("n_episodes and lanes_per_dir must be >= 1")
+    if int(lane_offset) % lpd:
+        raise ValueError("lane_offset (%d) must be a multiple of lanes_per_dir (%d)" % (lane_offset, lpd))
+    sign = np.asarray(sign)
+    n = len(sign)
+    if (int(lane_offset) + n) * K > (1 << 32):
+        raise ValueError("episode stream ids must lie in [0, 2^32): (lane_offset + n_lanes) * n_episodes is too large")
+    if mode is False:
+        return None
+    e = np.arange(K, dtype=np.int64)[None, :]
+    if mode == "batch":
+        return np.ascontiguousarray(np.broadcast_to(e, (n, K)))
+    g = int(lane_offset) + np.arange(n, dtype=np.int64)
+    first = np.where(sign != 0, g - g % lpd, g)
+    return first[:, None] * K + e
+
+
 class Worker(object):
-    def __init__(self, policy, agent, noise_source, strategy_handler, sigma=0.02, eval_prob=0.1, random_seed=123):
+    def __init__(self, policy, agent, noise_source, strategy_handler, sigma=0.02, eval_prob=0.1, random_seed=123,
+                 episodes_per_lane=1, common_random_numbers=False):
+        """episodes_per_lane = K: every lane's return is the mean over K episodes run in one launch;
+        common_random_numbers = False | "pair" (True) | "batch": which lanes share their episodes' resets and draws
+        (episode_stream_ids).  Either option routes launches to engine.rollout_episodes: MLP policies on a physics
+        env, table or counter noise only."""
         self.policy = policy
         self.agent = agent
         require_noise_source(noise_source, "Worker")
@@ -49,6 +93,20 @@ class Worker(object):
         self._lane_consts = {}  # (n_dirs, antithetic, lane_range, world, rank) -> the constant parts of _lanes_of
         self._next = None      # (key, host lanes, device lanes) uploaded ahead by evaluate(prefetch=True)
         self._launch_pairs = False  # the last launch's lanes were antithetic pairs (lane_novelty takes the pair form)
+        self.episodes_per_lane = int(episodes_per_lane)
+        self.crn = crn_mode(common_random_numbers)
+        if not 1 <= self.episodes_per_lane <= 1024:
+            raise ValueError("episodes_per_lane must be in 1 .. 1024")
+        self._episodes_route = self.episodes_per_lane > 1 or self.crn is not False
+        if self._episodes_route:
+            if self._host_noise:
+                raise ValueError("episodes_per_lane / common_random_numbers need a table or counter noise source "
+                                 "(host noise sources are not supported)")
+            from envs import _PhysicsEnv
+            if policy.KIND not in ("discrete", "mujoco") or not isinstance(agent.env, _PhysicsEnv):
+                raise ValueError("episodes_per_lane / common_random_numbers run MLP policies on the physics envs only "
+                                 "(CartPole, Pendulum, Acrobot, MountainCar, MountainCarContinuous)")
+        self.want_ret_sq = False   # launch() also asks for the lanes' sum of squared episode returns (res.reward_sq)
 
     # ---- hot path ---------------------------------------------------------------------------
     _RING = 64  # upload slots per lane count: an FDBatch's device idx / sign stay valid for the next 63 uploads
@@ -120,13 +178,15 @@ class Worker(object):
         return (arrs, ev) if defer_wait else arrs
 
     def launch(self, idx, sign, det, seed=None, out=None, jiggle=True, lane_offset=0, lanes_dev=None, pairs=False,
-               timing=None, rows=None, table=None):
+               timing=None, rows=None, table=None, lanes_per_dir=1):
         """Run one rollout over explicit lanes (host arrays) -> FDBatch (asynchronous).  lanes_dev: the same lanes
         already on the device (idx, sign, det), e.g. uploaded ahead by evaluate(prefetch=True).  pairs: lanes 2p,
         2p+1 are antithetic pairs (checked here) -- an Impala rollout then streams each pair's sigma-eps once
         (fdr_impala_desc.pairs).  timing: a (start, end) pair of torch.cuda.Event recorded on the stream right
         around the rollout launch(es), nothing else inside (bench.py's kernel-time pass).  table: the noise rows idx
-        points into, in place of the source's shared table (a CounterNoiseSource's rows of this launch)."""
+        points into, in place of the source's shared table (a CounterNoiseSource's rows of this launch).
+        lanes_per_dir: consecutive lanes of one direction, which share their random streams under
+        common_random_numbers="pair" (episode_stream_ids)."""
         p = self.policy
         n = len(idx)
         idx_d, sign_d, det_d = lanes_dev if lanes_dev is not None else self._lanes_to_device(idx, sign, det)
@@ -141,7 +201,7 @@ class Worker(object):
             lanes = engine.lanes_desc(p.flat, 0, table, idx_d, sign_d, self.sigma, det_d, lane_offset)
         bm, bv = p.bn_stats()
         if seed is None:
-            seed = self.agent.next_seed(n)
+            seed = self.agent.next_seed(n * self.episodes_per_lane)
         if p.KIND in ("impala", "atari"):
             # E envs per lane: returns are per (lane, env), lane-major; idx / sign / norm2 repeat per env
             E = self.agent.env.envs_per_lane
@@ -170,8 +230,16 @@ class Worker(object):
         if timing is not None:
             timing[0].record()
         self._launch_pairs = False
-        res = engine.rollout(p.spec, self.agent.env, lanes, n, seed, jiggle=jiggle, obs_mean=om, obs_std=osd,
-                             bn_mean=bm, bn_var=bv, out=out, device=p.flat.device, obs_stats=chance)
+        if self._episodes_route:
+            K = self.episodes_per_lane
+            ids = episode_stream_ids(self.crn, sign, lane_offset, K, lanes_per_dir)
+            ids_d = None if ids is None else torch.from_numpy(ids).to(p.flat.device)
+            res = engine.rollout_episodes(p.spec, self.agent.env, lanes, n, seed, K, episode_ids=ids_d, jiggle=jiggle,
+                                          obs_mean=om, obs_std=osd, bn_mean=bm, bn_var=bv, obs_stats=chance,
+                                          ret_sq=self.want_ret_sq, out=out, device=p.flat.device)
+        else:
+            res = engine.rollout(p.spec, self.agent.env, lanes, n, seed, jiggle=jiggle, obs_mean=om, obs_std=osd,
+                                 bn_mean=bm, bn_var=bv, out=out, device=p.flat.device, obs_stats=chance)
         if timing is not None:
             timing[1].record()
         return res, idx_d, sign_d
@@ -265,7 +333,7 @@ class Worker(object):
         lpd = 2 if antithetic else 1
         lo = 0 if lane_range is None else lane_range[0]
         res, idx_d, sign_d = self.launch(lidx, sign, det, seed=seed, out=out, lane_offset=lo, lanes_dev=lanes_dev,
-                                         pairs=antithetic, timing=timing)
+                                         pairs=antithetic, timing=timing, lanes_per_dir=lpd)
         if prefetch and hasattr(self.noise_source, "peek_batch"):
             nidx = self.noise_source.peek_batch(n_dirs)
             nl, ns, nd, _, _ = self._lanes_of(nidx, n_dirs, antithetic, key[2])
@@ -273,7 +341,7 @@ class Worker(object):
         E = getattr(self.agent.env, "envs_per_lane", 1)
         if E > 1:
             lidx, sign = np.repeat(lidx, E), np.repeat(sign, E)
-        if getattr(self.agent.env, "terminates", False):   # episodes end before T: count the steps taken
+        if getattr(self.agent.env, "terminates", False) or self._episodes_route:   # count the steps taken
             self.agent.add_timesteps(res.timesteps)
         else:
             self.agent.cumulative_timesteps += int(len(lidx)) * self.agent.env.episode_len
@@ -353,12 +421,12 @@ class Worker(object):
         lidx, lanes_dev = c
         rows = self._counter_rows(ids[d_lo] if nd else 0, nd)
         res, idx_d, sign_d = self.launch(lidx, sign, det, seed=seed, out=out, lane_offset=lo, lanes_dev=lanes_dev,
-                                         pairs=antithetic, timing=timing, table=rows)
+                                         pairs=antithetic, timing=timing, table=rows, lanes_per_dir=lpd)
         E = getattr(self.agent.env, "envs_per_lane", 1)
         enc = [e for e in map(str, ids[d_lo:d_lo + nd].tolist()) for _ in range(lpd * E)]
         if E > 1:
             lidx, sign = np.repeat(lidx, E), np.repeat(sign, E)
-        if getattr(self.agent.env, "terminates", False):
+        if getattr(self.agent.env, "terminates", False) or self._episodes_route:
             self.agent.add_timesteps(res.timesteps)
         else:
             self.agent.cumulative_timesteps += int(len(lidx)) * self.agent.env.episode_len
@@ -391,13 +459,14 @@ class Worker(object):
             ids = self.noise_source.sample_ids(k)
             table = self._counter_rows(ids[0] if k else 0, k)
             idx[~is_eval] = np.arange(k, dtype=np.int64) * self.noise_source.row_stride
-            res, idx_d, sign_d = self.launch(idx, sign, is_eval.astype(np.int8), jiggle=False, table=table)
+            res, idx_d, sign_d = self.launch(idx, sign, is_eval.astype(np.int8), jiggle=False, table=table,
+                                             lanes_per_dir=1)
             it = iter(ids)
             enc = ["0" if e else str(int(next(it))) for e in is_eval]
         else:
             if k:
                 idx[~is_eval] = self.noise_source.sample_batch(k)
-            res, idx_d, sign_d = self.launch(idx, sign, is_eval.astype(np.int8), jiggle=False)
+            res, idx_d, sign_d = self.launch(idx, sign, is_eval.astype(np.int8), jiggle=False, lanes_per_dir=1)
         nov = self.lane_novelty(idx_d, sign_d, table=table if host_rows is None else host_rows.table)
         E = getattr(self.agent.env, "envs_per_lane", 1)
         if E > 1:

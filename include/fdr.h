@@ -215,6 +215,31 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
                    const float* obs_mean, const float* obs_std, double* ret, double* ent, int32_t* steps,
                    double* norm2, const fdr_rollout_extras* extras, fdr_stream stream);
 
+/* ---- K episodes per lane, caller-chosen random streams (added within fdr 0.5: one export, no struct) ----------
+ * The physics envs only (FDR_ENV_CARTPOLE .. FDR_ENV_MOUNTAINCAR_CONT, each at its one policy; descriptor rules as
+ * fdr_rollout_ex; any other env kind: FDR_ERR_UNSUPPORTED, nothing launched).  Lane l forms theta'_l once and runs
+ * n_episodes = K episodes (1 .. 1024, else FDR_ERR_INVALID) in ONE launch.  Episode e of lane l is exactly the
+ * episode fdr_rollout runs for global lane id
+ *   id(l, e) = episode_ids[l * K + e]            (device [n_lanes, K] i64), or
+ *   id(l, e) = (lanes->lane_offset + l) * K + e  with episode_ids == NULL  (K = 1: fdr_rollout's own lane id):
+ * the reset draws, the action draws and the obs-statistics coins are keyed by id(l, e).  Lanes given equal ids
+ * play under common random numbers.  PRECONDITION: every id lies in [0, 2^32) (it fills the counter's lane field;
+ * not checked on the device).  The jiggle stays keyed by the physical lane lane_offset + l, so lanes sharing
+ * streams still get distinct tie-breakers.  The lane's deterministic flag holds for all K episodes.
+ *   ret    [n_lanes] f64  (((R_0 + R_1) + ...) + R_{K-1}) / K of the episodes' reward sums (+ jiggle)
+ *   ret_sq [n_lanes] f64  sum_e R_e^2 (nullable): within-lane variance = ret_sq / K - mean^2
+ *   ent    [n_lanes] f64  (sum_e S_e) / (sum_e n_e): mean entropy over all visited states
+ *   steps  [n_lanes] i32  sum_e n_e
+ *   norm2  [n_lanes] f64  as fdr_rollout, written once (nullable)
+ *   os_mean / os_m2 [n_lanes, n_in] f32, os_count [n_lanes] i32: all NULL, or all set (else FDR_ERR_INVALID): one
+ *           Welford statistic per lane running on across the K episodes, sampled with chance os_chance per step.
+ * No state recording and no injected draws on this route. */
+int fdr_rollout_episodes(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_desc* env,
+                         const fdr_lanes_desc* lanes, int32_t n_lanes, uint64_t seed, int32_t jiggle,
+                         const float* obs_mean, const float* obs_std, int32_t n_episodes, const int64_t* episode_ids,
+                         double* ret, double* ret_sq, double* ent, int32_t* steps, double* norm2, float* os_mean,
+                         float* os_m2, int32_t* os_count, float os_chance, fdr_stream stream);
+
 /* ---- noise-table index draw on the HOST (utils/noise_sources.py:44-47) -----------------------------
  * out[i], i < n: the indices n successive RandomState.randint(0, max_idx) calls return, drawn from the MT19937
  * state key [624] u32 / *pos (numpy RandomState.get_state()[1:3]) and advanced in place: 32-bit words masked by

@@ -2,8 +2,11 @@
 batch_size=2048, antithetic=True) with the reference's hyperparameters for 300 epochs, once per weighting.  "train" is
 the mean return of the epoch's sampled training lanes averaged over the 10 epochs before the row, "eval" the mean return
 over 64 deterministic lanes of theta from 64 different resets, "done" the share of those 64 that reached the goal.
+--episodes K / --crn {none,pair,batch}: the runner's episodes_per_lane and common_random_numbers -- every lane, the 64
+eval lanes too, then returns the mean of K episodes, and "done" is the share of eval lanes with an episode that ended
+before the time limit.
 
-    python tools/physics_learning.py [env_id ...] [--epochs 300]
+    python tools/physics_learning.py [env_id ...] [--epochs 300] [--episodes K] [--crn none|pair|batch]
 """
 import argparse
 import os
@@ -22,8 +25,9 @@ from run_sequential import SequentialRunner  # noqa: E402
 IDS = ["Acrobot-v1", "MountainCar-v0", "MountainCarContinuous-v0"]
 
 
-def run(env_id, weighting, epochs, every):
-    r = SequentialRunner(env_id=env_id, physics=True, batch_size=2048, antithetic=True, verbose=False)
+def run(env_id, weighting, epochs, every, episodes=1, crn=False):
+    r = SequentialRunner(env_id=env_id, physics=True, batch_size=2048, antithetic=True, verbose=False,
+                         episodes_per_lane=episodes, common_random_numbers=crn)
     r.learner.weighting = weighting
     launch = r.worker.launch
     train, rows = [], []
@@ -34,7 +38,7 @@ def run(env_id, weighting, epochs, every):
                      jiggle=False)[0]
         ret, steps = res.reward.cpu().numpy(), res.timesteps.cpu().numpy()
         recent = np.mean(train[-10:]) if train else float("nan")
-        rows.append((epoch, recent, float(ret.mean()), float((steps < r.env.episode_len).mean())))
+        rows.append((epoch, recent, float(ret.mean()), float((steps < episodes * r.env.episode_len).mean())))
 
     def spy(idx, sign, det, **kw):
         if len(train) % every == 0:
@@ -56,11 +60,14 @@ def main():
     ap.add_argument("env_ids", nargs="*", default=IDS)
     ap.add_argument("--epochs", type=int, default=300)
     ap.add_argument("--every", type=int, default=50)
+    ap.add_argument("--episodes", type=int, default=1)
+    ap.add_argument("--crn", choices=("none", "pair", "batch"), default="none")
     a = ap.parse_args()
+    crn = False if a.crn == "none" else a.crn
     for env_id in a.env_ids:
-        res = {w: run(env_id, w, a.epochs, a.every) for w in ("zscore", "centred_rank")}
-        print("%s: %d epochs, wall %.1f s (z-score) / %.1f s (centred rank)"
-              % (env_id, a.epochs, res["zscore"][1], res["centred_rank"][1]))
+        res = {w: run(env_id, w, a.epochs, a.every, a.episodes, crn) for w in ("zscore", "centred_rank")}
+        print("%s, K = %d, crn %s: %d epochs, wall %.1f s (z-score) / %.1f s (centred rank)"
+              % (env_id, a.episodes, a.crn, a.epochs, res["zscore"][1], res["centred_rank"][1]))
         print("| epoch | z-score: train | z-score: eval (done) | centred rank: train | centred rank: eval (done) |")
         print("|---|---|---|---|---|")
         for z, c in zip(res["zscore"][0], res["centred_rank"][0]):

@@ -251,15 +251,15 @@ int fdr_obs_stats_merge(fdr_ctx* ctx, const float* mean, const float* m2, const 
   return launch_obs_stats_merge(mean, m2, count, n, dim, acc_mean, acc_m2, acc_count, (hipStream_t)stream);
 }
 
-int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_desc* env,
-                   const fdr_lanes_desc* lanes, int32_t n_lanes, uint64_t seed, int32_t jiggle,
-                   const float* obs_mean, const float* obs_std, double* ret, double* ent, int32_t* steps,
-                   double* norm2, const fdr_rollout_extras* extras, fdr_stream stream) {
-  FDR_CTX(ctx, C);
-  PolicyKey k;
+// fdr_rollout_ex's and fdr_rollout_episodes' shared refusals in their one order, then k and a filled for the launch.
+// own_checks: the caller's own refusals, behind the checks of each argument alone, before the env against the policy.
+extern "C++" template <class OwnChecks>
+static int rollout_args(const fdr_policy_desc* policy, const fdr_env_desc* env, const fdr_lanes_desc* lanes,
+                        int32_t n_lanes, uint64_t seed, int32_t jiggle, const float* obs_mean, const float* obs_std,
+                        double* ret, double* ent, int32_t* steps, double* norm2, OwnChecks&& own_checks, PolicyKey& k,
+                        RolloutArgs& a) {
   int rc = policy_key(policy, &k);
   if (rc) return rc;
-  RolloutArgs a;
   std::memset(&a, 0, sizeof(a));
   rc = lanes_args(lanes, n_lanes, k.n_params, &a.lanes);
   if (rc) return rc;
@@ -269,6 +269,8 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
     return set_error(FDR_ERR_INVALID, "obs_mean and obs_std must both be given or both NULL");
   if (env->episode_len <= 0 || env->episode_len >= (1 << 28))
     return set_error(FDR_ERR_INVALID, "episode_len out of range");
+  rc = own_checks();
+  if (rc) return rc;
   const PhysicsEnv* const pe = physics_env(env->kind);
   if (pe) {
     // the descriptor on its own first (INVALID), then the policy it is paired with (UNSUPPORTED)
@@ -298,7 +300,6 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
   } else {
     return set_error(FDR_ERR_INVALID, "unknown env kind");
   }
-  if (n_lanes == 0) return FDR_OK;
   a.n_lanes = n_lanes;
   a.T = env->episode_len;
   a.key = mix64(seed);
@@ -322,6 +323,19 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
   a.ent = ent;
   a.steps = steps;
   a.norm2 = norm2;
+  return FDR_OK;
+}
+
+int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_desc* env,
+                   const fdr_lanes_desc* lanes, int32_t n_lanes, uint64_t seed, int32_t jiggle,
+                   const float* obs_mean, const float* obs_std, double* ret, double* ent, int32_t* steps,
+                   double* norm2, const fdr_rollout_extras* extras, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  PolicyKey k;
+  RolloutArgs a;
+  const int rc = rollout_args(policy, env, lanes, n_lanes, seed, jiggle, obs_mean, obs_std, ret, ent, steps, norm2,
+                              [] { return FDR_OK; }, k, a);
+  if (rc || n_lanes == 0) return rc;
   if (extras) {
     a.states = extras->states;
     if (extras->obs_mean || extras->obs_m2 || extras->obs_count) {
@@ -346,55 +360,25 @@ int fdr_rollout_episodes(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_
                          float* os_m2, int32_t* os_count, float os_chance, fdr_stream stream) {
   FDR_CTX(ctx, C);
   PolicyKey k;
-  int rc = policy_key(policy, &k);
-  if (rc) return rc;
-  RolloutArgs a;
-  std::memset(&a, 0, sizeof(a));
-  rc = lanes_args(lanes, n_lanes, k.n_params, &a.lanes);
-  if (rc) return rc;
-  if (!env) return set_error(FDR_ERR_INVALID, "env desc is NULL");
-  if (!ret || !ent || !steps) return set_error(FDR_ERR_INVALID, "NULL output");
-  if ((obs_mean == nullptr) != (obs_std == nullptr))
-    return set_error(FDR_ERR_INVALID, "obs_mean and obs_std must both be given or both NULL");
-  if (env->episode_len <= 0 || env->episode_len >= (1 << 28))
-    return set_error(FDR_ERR_INVALID, "episode_len out of range");
-  // K * episode_len <= 1024 * 10000 stays within the int32 steps
-  if (n_episodes < 1 || n_episodes > 1024) return set_error(FDR_ERR_INVALID, "n_episodes must be 1 .. 1024");
-  if (os_mean || os_m2 || os_count) {
-    if (!os_mean || !os_m2 || !os_count)
-      return set_error(FDR_ERR_INVALID, "os_mean, os_m2 and os_count must be given together");
-  }
-  const PhysicsEnv* const pe = physics_env(env->kind);
-  if (!pe) return set_error(FDR_ERR_UNSUPPORTED, "fdr_rollout_episodes runs the physics envs only");
-  // the descriptor on its own first (INVALID), then the policy it is paired with (UNSUPPORTED): as fdr_rollout_ex
-  if (env->M || env->K || env->s0 || env->walkable)
-    return set_error(FDR_ERR_INVALID, "physics envs take no M, K, s0 or walkable");
-  if (env->done_threshold != 0.f) return set_error(FDR_ERR_INVALID, "physics envs take done_threshold 0");
-  if (env->obs_dim != pe->obs || env->act_dim != pe->act)
-    return set_error(FDR_ERR_INVALID, "obs_dim / act_dim are not this physics env's own");
-  if (env->episode_len > 10000) return set_error(FDR_ERR_INVALID, "physics env episode_len must be 1 .. 10000");
-  if (!physics_policy_ok(*pe, k)) return set_error(FDR_ERR_UNSUPPORTED, pe->policy_msg);
-  if (n_lanes == 0) return FDR_OK;
-  a.n_lanes = n_lanes;
-  a.T = env->episode_len;
-  a.key = mix64(seed);
-  a.jiggle = jiggle;
-  a.bn_mean = policy->bn_mean;
-  a.bn_var = policy->bn_var;
-  a.obs_mean = obs_mean;
-  a.obs_std = obs_std;
-  a.ret = ret;
-  a.ent = ent;
-  a.steps = steps;
-  a.norm2 = norm2;
-  if (os_mean) {
-    a.os_mean = os_mean;
-    a.os_m2 = os_m2;
-    a.os_count = os_count;
-    a.os_chance = os_chance;
-  }
   EpisodesArgs ea;
-  ea.r = a;
+  auto own_checks = [&] {
+    // K * episode_len <= 1024 * 10000 stays within the int32 steps
+    if (n_episodes < 1 || n_episodes > 1024) return set_error(FDR_ERR_INVALID, "n_episodes must be 1 .. 1024");
+    if ((os_mean || os_m2 || os_count) && (!os_mean || !os_m2 || !os_count))
+      return set_error(FDR_ERR_INVALID, "os_mean, os_m2 and os_count must be given together");
+    if (!physics_env(env->kind))
+      return set_error(FDR_ERR_UNSUPPORTED, "fdr_rollout_episodes runs the physics envs only");
+    return (int)FDR_OK;
+  };
+  const int rc = rollout_args(policy, env, lanes, n_lanes, seed, jiggle, obs_mean, obs_std, ret, ent, steps, norm2,
+                              own_checks, k, ea.r);
+  if (rc || n_lanes == 0) return rc;
+  if (os_mean) {
+    ea.r.os_mean = os_mean;
+    ea.r.os_m2 = os_m2;
+    ea.r.os_count = os_count;
+    ea.r.os_chance = os_chance;
+  }
   ea.n_episodes = n_episodes;
   ea.episode_ids = episode_ids;
   ea.ret_sq = ret_sq;

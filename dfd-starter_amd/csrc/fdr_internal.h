@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
+
 #include "fdr_common.h"
 
 namespace fdr {
@@ -125,20 +127,53 @@ int launch_rollout(const Context& ctx, const PolicyKey& k, int env_kind, const R
 // synthetic env, one lane per wave: the 128-VGPR kernel / the 256-VGPR one
 int launch_rollout_lane(const PolicyKey& k, const RolloutArgs& args, hipStream_t stream);
 int launch_rollout_wide(const PolicyKey& k, const RolloutArgs& args, hipStream_t stream);
-// The classic-control physics envs: each kind with its own observation / action sizes and the one policy it runs
-// under.  fdr_rollout_ex validates the descriptor against this table and launch_rollout_env the policy.
+// The classic-control physics envs, the one table of them: each kind with its observation / action sizes, the one
+// policy it runs under, the refusal of any other and its kernels' display names.  The kernels' shape checks, the
+// shapes compiled for them (fdr_mlp.h: PhysicsShapes), the runtime table and both launchers derive from it.
+template <int KIND>
+struct PhysicsSpec;
+#define FDR_PHYSICS_SPEC(KIND, NIN_, NA_, DISC_, TAG, POLICY_MSG)                                                  \
+  template <>                                                                                                      \
+  struct PhysicsSpec<KIND> {                                                                                       \
+    static constexpr int ENV = KIND, NIN = NIN_, NA = NA_;                                                         \
+    static constexpr bool DISC = DISC_;                                                                            \
+    static constexpr const char *policy_msg = POLICY_MSG, *rollout_name = "rollout_kernel<" TAG ">",               \
+                                *episodes_name = "rollout_episodes_kernel<" TAG ">";                               \
+    template <int I, int A, bool D>                                                                                \
+    static constexpr bool is_shape() { return I == NIN_ && A == NA_ && D == DISC_; }                               \
+  }
+FDR_PHYSICS_SPEC(FDR_ENV_CARTPOLE, 4, 2, true, "cartpole", "CartPole needs a DiscretePolicy(4, 2)");
+FDR_PHYSICS_SPEC(FDR_ENV_PENDULUM, 3, 1, false, "pendulum", "Pendulum needs a MujocoPolicy(3, 1)");
+FDR_PHYSICS_SPEC(FDR_ENV_ACROBOT, 6, 3, true, "acrobot", "Acrobot needs a DiscretePolicy(6, 3)");
+FDR_PHYSICS_SPEC(FDR_ENV_MOUNTAINCAR, 2, 3, true, "mountaincar", "MountainCar needs a DiscretePolicy(2, 3)");
+FDR_PHYSICS_SPEC(FDR_ENV_MOUNTAINCAR_CONT, 2, 1, false, "mountaincar_cont",
+                 "MountainCarContinuous needs a MujocoPolicy(2, 1)");
+#undef FDR_PHYSICS_SPEC
+template <int... KIND>
+struct PhysicsKinds {};
+using PhysicsEnvKinds = PhysicsKinds<FDR_ENV_CARTPOLE, FDR_ENV_PENDULUM, FDR_ENV_ACROBOT, FDR_ENV_MOUNTAINCAR,
+                                     FDR_ENV_MOUNTAINCAR_CONT>;
+// f(PhysicsSpec<kind>{}) for the physics env `kind`; false (f not called): not a physics env
+template <class F, int... KIND>
+bool with_physics_env(int kind, F&& f, PhysicsKinds<KIND...>) {
+  return ((kind == KIND && (f(PhysicsSpec<KIND>{}), true)) || ...);
+}
+template <class F>
+bool with_physics_env(int kind, F&& f) {
+  return with_physics_env(kind, f, PhysicsEnvKinds{});
+}
+// The spec as runtime values: fdr_rollout_ex validates the descriptor against it, the launchers the policy.
 struct PhysicsEnv {
   int kind, obs, act;
   bool discrete;
   const char* policy_msg;
 };
-constexpr PhysicsEnv kPhysicsEnvs[] = {
-    {FDR_ENV_CARTPOLE, 4, 2, true, "CartPole needs a DiscretePolicy(4, 2)"},
-    {FDR_ENV_PENDULUM, 3, 1, false, "Pendulum needs a MujocoPolicy(3, 1)"},
-    {FDR_ENV_ACROBOT, 6, 3, true, "Acrobot needs a DiscretePolicy(6, 3)"},
-    {FDR_ENV_MOUNTAINCAR, 2, 3, true, "MountainCar needs a DiscretePolicy(2, 3)"},
-    {FDR_ENV_MOUNTAINCAR_CONT, 2, 1, false, "MountainCarContinuous needs a MujocoPolicy(2, 1)"},
-};
+template <int... KIND>
+constexpr std::array<PhysicsEnv, sizeof...(KIND)> physics_table(PhysicsKinds<KIND...>) {
+  return {{{KIND, PhysicsSpec<KIND>::NIN, PhysicsSpec<KIND>::NA, PhysicsSpec<KIND>::DISC,
+            PhysicsSpec<KIND>::policy_msg}...}};
+}
+inline constexpr auto kPhysicsEnvs = physics_table(PhysicsEnvKinds{});
 inline const PhysicsEnv* physics_env(int kind) {  // NULL: not a physics env
   for (const PhysicsEnv& e : kPhysicsEnvs)
     if (e.kind == kind) return &e;

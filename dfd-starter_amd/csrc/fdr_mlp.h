@@ -145,19 +145,31 @@ struct ShapeList {};
 // every kernel family: forward, both loaders, rollout_kernel (synthetic env, one-lane and WIDE), rollout_pair_kernel
 using MlpShapes = ShapeList<Shape<2, 9, true>, Shape<4, 2, true>, Shape<8, 4, true>, Shape<17, 6, false>,
                             Shape<11, 3, false>, Shape<8, 2, false>>;
-// Shapes only the physics envs use (Pendulum's MujocoPolicy(3, 1), Acrobot's DiscretePolicy(6, 3), MountainCar's
-// DiscretePolicy(2, 3), MountainCarContinuous's MujocoPolicy(2, 1)): the one-lane rollout of their env, the batched
-// forward and the lane loader's read-back -- no synthetic-env, pair or WIDE instance
-using PhysicsShapes = ShapeList<Shape<3, 1, false>, Shape<6, 3, true>, Shape<2, 3, true>, Shape<2, 1, false>>;
-static_assert(Layout<3, 1, false>::P == 4546, "MujocoPolicy(3, 1) has 4546 parameters");
-static_assert(Layout<6, 3, true>::P == 5071, "DiscretePolicy(6, 3) has 5071 parameters");
-static_assert(Layout<2, 3, true>::P == 4807, "DiscretePolicy(2, 3) has 4807 parameters");
-static_assert(Layout<2, 1, false>::P == 4482, "MujocoPolicy(2, 1) has 4482 parameters");
-
 template <class S, class... T>
 constexpr bool shape_in(ShapeList<T...>) {
   return (std::is_same_v<S, T> || ...);
 }
+// Shapes only the physics envs use: every PhysicsSpec shape (fdr_internal.h) that MlpShapes lacks, in the table's
+// order (all but CartPole's).  They get the one-lane rollout of their env, the batched forward and the lane loader's
+// read-back -- no synthetic-env, pair or WIDE instance.
+template <class List, int... KIND>
+struct PhysicsOnly {
+  using type = List;
+};
+template <class... T, int K, int... KIND>
+struct PhysicsOnly<ShapeList<T...>, K, KIND...> {
+  using S = Shape<PhysicsSpec<K>::NIN, PhysicsSpec<K>::NA, PhysicsSpec<K>::DISC>;
+  using Own = ShapeList<T...>;
+  using type = typename PhysicsOnly<std::conditional_t<shape_in<S>(MlpShapes{}) || shape_in<S>(Own{}), Own,
+                                                       ShapeList<T..., S>>, KIND...>::type;
+};
+template <int... KIND>
+typename PhysicsOnly<ShapeList<>, KIND...>::type physics_only_shapes(PhysicsKinds<KIND...>);
+using PhysicsShapes = decltype(physics_only_shapes(PhysicsEnvKinds{}));
+static_assert(Layout<3, 1, false>::P == 4546, "MujocoPolicy(3, 1) has 4546 parameters");
+static_assert(Layout<6, 3, true>::P == 5071, "DiscretePolicy(6, 3) has 5071 parameters");
+static_assert(Layout<2, 3, true>::P == 4807, "DiscretePolicy(2, 3) has 4807 parameters");
+static_assert(Layout<2, 1, false>::P == 4482, "MujocoPolicy(2, 1) has 4482 parameters");
 
 // Match k's (n_in, n_act, discrete) against the compiled shapes (MlpShapes, then PhysicsShapes when PHYSICS -- a
 // template parameter: f is instantiated for the lists it can be called with, no more), check n_params against the

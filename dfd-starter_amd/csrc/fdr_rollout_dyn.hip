@@ -15,6 +15,7 @@
 // The draws use the compiled kernels' counters -- hash_ctr(key, global lane, t, k) -- so a lane's stream does not
 // depend on the kernel that runs it.
 #include "fdr_mlp_dyn.h"
+#include "fdr_rollout_parts.h"
 
 namespace fdr {
 
@@ -53,11 +54,7 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, 4) void rollout_dyn_kernel(Rol
   const bool det = a.lanes.deterministic ? a.lanes.deterministic[lane] != 0 : false;
   Lane pl;
   pl.load(lay, src, j, a.bn_mean, a.bn_var, wtile + wv * lay.tile_f4());
-  {  // written now (rollout_kernel: a double live across the step loop would be spilled)
-    double n2 = wave_sum(src.n2);
-    asm volatile("" : "+v"(n2));
-    if (j == 0 && a.norm2) a.norm2[lane] = n2;
-  }
+  write_norm2(a, lane, j, src.n2);
 
   const bool f_states = (feat & kFeatStates) != 0, f_stats = (feat & kFeatObsStats) != 0,
              f_norm = (feat & kFeatObsNorm) != 0, f_inject = (feat & kFeatInject) != 0,
@@ -189,17 +186,7 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, 4) void rollout_dyn_kernel(Rol
     episode(std::false_type{});
 
   // ---- epilogue ----
-  eacc *= 0.693147180559945309f;  // log2 -> ln (both kinds)
-  const double esum = wave_sum((j < n_act) ? (double)eacc : 0.0);
-  if (j == 0) {
-    double r = racc;
-    if (a.jiggle) r += (hash_ctr(key, ulane, kJiggleT, 15) & 1ull) ? 1e-12 : -1e-12;
-    a.ret[lane] = r;
-    double e = esum / (double)nsteps;  // mean over the visited states (agent.py:60-65)
-    if constexpr (!DISC) e += (double)n_act * 1.4189385332046727;  // 0.5 + 0.5*ln(2*pi) per dim
-    a.ent[lane] = e;
-    a.steps[lane] = nsteps;
-  }
+  store_results<DISC>(a, lane, j, ulane, racc, entropy_sum(eacc, j, n_act), nsteps, n_act);
   if (f_stats) {
     if (j < n_in) {
       a.os_mean[(int64_t)lane * n_in + j] = os_mean;

@@ -3,106 +3,13 @@
 // (synthetic env), fdr_rollout_wide.hip (WIDE) and fdr_rollout_env.hip (trap, CartPole, Pendulum, Acrobot, MountainCar,
 // MountainCarContinuous).
 #pragma once
-#include "fdr_mlp_lane.h"
+#include "fdr_rollout_parts.h"
 
 namespace fdr {
 
 // trap-env observation (environment.py:59-61): python f64 division, cast to f32 by the policy
 __device__ __forceinline__ float trap_obs(int j, int col, int row) {
   return j == 0 ? (float)((double)(col * 7) / 1918.0) : (float)((double)(row * 7) / 1071.0);
-}
-
-// ---- classic-control physics envs (gym classic_control cartpole.py / pendulum.py / acrobot.py / mountain_car.py /
-// continuous_mountain_car.py in f32) ----
-// The state is a few scalars every thread of the wave holds identically (as the trap env's col / row).
-constexpr float kPiF = 3.14159274101257324f;     // fl32(pi)
-constexpr float kTwoPiF = 6.28318548202514648f;  // fl32(2 pi)
-// Reset draw i of a lane: the reserved counter slot t = kJiggleT, k = i (k = 15 there is the jiggle's; action draws
-// have t < 10000), scaled to gym's uniform range as fl32(fl32(scale * u) - shift) -- no contraction: compared bitwise.
-__device__ __forceinline__ float physics_reset(uint64_t key, uint64_t ulane, int i, float scale, float shift) {
-#pragma clang fp contract(off)
-  const float v = scale * uniform24(hash_ctr(key, ulane, kJiggleT, (uint64_t)i));
-  return v - shift;
-}
-// ((th + pi) mod 2 pi) - pi, floor-mod
-__device__ __forceinline__ float wrap_pi(float th) {
-  const float y = th + kPiF;
-  return (y - kTwoPiF * floorf(y * (1.0f / kTwoPiF))) - kPiF;
-}
-// CartPole-v1, explicit Euler (positions advance with the old velocities); returns the failure test of the new state
-__device__ __forceinline__ bool cartpole_step(float& x, float& xd, float& th, float& thd, int act) {
-  const float force = act == 1 ? 10.f : -10.f;
-  const float sn = sinf(th), cs = cosf(th);
-  const float temp = (force + 0.05f * thd * thd * sn) / 1.1f;
-  const float thacc = (9.8f * sn - cs * temp) / (0.5f * (4.0f / 3.0f - 0.1f * cs * cs / 1.1f));
-  const float xacc = temp - 0.05f * thacc * cs / 1.1f;
-  x += 0.02f * xd;
-  xd += 0.02f * xacc;
-  th += 0.02f * thd;
-  thd += 0.02f * thacc;
-  constexpr float kThetaThr = 0.20943951023931953f;  // 12 * 2 pi / 360
-  return x < -2.4f || x > 2.4f || th < -kThetaThr || th > kThetaThr;
-}
-// Pendulum-v1 (g = 10, m = l = 1, dt = 0.05): sn = sin(th) on entry; th is kept wrapped, (cs, sn) follow it.
-// Returns the reward -cost of the pre-step state.
-__device__ __forceinline__ float pendulum_step(float& th, float& thd, float& cs, float& sn, float a) {
-  const float u = fminf(fmaxf(a, -2.f), 2.f);
-  const float w = wrap_pi(th);
-  const float cost = w * w + 0.1f * thd * thd + 0.001f * u * u;
-  thd = fminf(fmaxf(thd + (15.f * sn + 3.f * u) * 0.05f, -8.f), 8.f);
-  th = wrap_pi(th + thd * 0.05f);
-  cs = cosf(th);
-  sn = sinf(th);
-  return -cost;
-}
-// Acrobot-v1 ("book" dynamics: m1 = m2 = l1 = I1 = I2 = 1, lc1 = lc2 = 0.5, g = 9.8, no torque noise): the
-// accelerations of (th1, th2) at velocities (d1, d2) under torque tq.  gym's cos(. - pi / 2) is taken as the sine.
-__device__ __forceinline__ void acrobot_dsdt(float th1, float th2, float d1, float d2, float tq, float& a1, float& a2) {
-  float sn2, cs2;
-  sincosf(th2, &sn2, &cs2);
-  const float dd1 = 0.25f + (1.25f + cs2) + 2.f;  // m1 lc1^2 + m2 (l1^2 + lc2^2 + 2 l1 lc2 cos th2) + I1 + I2
-  const float dd2 = (0.25f + 0.5f * cs2) + 1.f;   // m2 (lc2^2 + l1 lc2 cos th2) + I2
-  const float phi2 = 4.9f * sinf(th1 + th2);
-  const float phi1 = -0.5f * d2 * d2 * sn2 - d2 * d1 * sn2 + 14.7f * sinf(th1) + phi2;
-  a2 = (tq + dd2 / dd1 * phi1 - 0.5f * d1 * d1 * sn2 - phi2) / (1.25f - dd2 * dd2 / dd1);
-  a1 = -(dd2 * a2 + phi1) / dd1;
-}
-// one classical RK4 step over [0, 0.2], then gym's wrap of the angles (one conditional 2 pi: |thd| dt < 2 pi) and
-// clamp of the velocities; returns the success test of the new state (the free end above the bar by one link)
-__device__ __forceinline__ bool acrobot_step(float& th1, float& th2, float& d1, float& d2, int act) {
-  const float tq = (float)(act - 1);
-  constexpr float h = 0.2f, h2 = 0.1f, h6 = 0.2f / 6.0f;
-  float k1a, k1b, k2a, k2b, k3a, k3b, k4a, k4b;
-  acrobot_dsdt(th1, th2, d1, d2, tq, k1a, k1b);
-  const float u1 = d1 + h2 * k1a, u2 = d2 + h2 * k1b;  // the stages' velocities: the angles' derivatives
-  acrobot_dsdt(th1 + h2 * d1, th2 + h2 * d2, u1, u2, tq, k2a, k2b);
-  const float v1 = d1 + h2 * k2a, v2 = d2 + h2 * k2b;
-  acrobot_dsdt(th1 + h2 * u1, th2 + h2 * u2, v1, v2, tq, k3a, k3b);
-  const float w1 = d1 + h * k3a, w2 = d2 + h * k3b;
-  acrobot_dsdt(th1 + h * v1, th2 + h * v2, w1, w2, tq, k4a, k4b);
-  th1 += h6 * (d1 + 2.f * u1 + 2.f * v1 + w1);
-  th2 += h6 * (d2 + 2.f * u2 + 2.f * v2 + w2);
-  d1 += h6 * (k1a + 2.f * k2a + 2.f * k3a + k4a);
-  d2 += h6 * (k1b + 2.f * k2b + 2.f * k3b + k4b);
-  th1 = th1 > kPiF ? th1 - kTwoPiF : (th1 < -kPiF ? th1 + kTwoPiF : th1);
-  th2 = th2 > kPiF ? th2 - kTwoPiF : (th2 < -kPiF ? th2 + kTwoPiF : th2);
-  d1 = fminf(fmaxf(d1, -4.f * kPiF), 4.f * kPiF);
-  d2 = fminf(fmaxf(d2, -9.f * kPiF), 9.f * kPiF);
-  return -cosf(th1) - cosf(th1 + th2) > 1.f;
-}
-// observation element j of (cos th1, sin th1, cos th2, sin th2, thd1, thd2)
-__device__ __forceinline__ float acrobot_obs(int j, float th1, float th2, float d1, float d2) {
-  float sn, cs;
-  sincosf(j < 2 ? th1 : th2, &sn, &cs);
-  return j < 4 ? ((j & 1) ? sn : cs) : (j == 4 ? d1 : d2);
-}
-// MountainCar-v0 / MountainCarContinuous-v0: force * power already formed (discrete (a - 1) 0.001, continuous
-// clamp(a, +-1) 0.0015), goal 0.5 / 0.45; the car stops at the left wall.  Returns the success test of the new state.
-__device__ __forceinline__ bool mountaincar_step(float& pos, float& vel, float push, float goal) {
-  vel = fminf(fmaxf(vel + push - 0.0025f * cosf(3.f * pos), -0.07f), 0.07f);
-  pos = fminf(fmaxf(pos + vel, -1.2f), 0.6f);
-  if (pos == -1.2f && vel < 0.f) vel = 0.f;
-  return pos >= goal && vel >= 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -113,10 +20,10 @@ __device__ __forceinline__ bool mountaincar_step(float& pos, float& vel, float p
 // (u_inject); kFeatTerm: terminating synthetic env (fdr_env_desc.done_threshold): the lane's episode ends after the
 // step whose next state has |s'[done_dim]| > done_threshold (worker/agent.py:50-52: done -> break), or at T
 // (one lane per wave: the wave leaves its loop -- only these instances carry the test)
-// ENV: FDR_ENV_SYNTH, FDR_ENV_TRAP, or a physics env (FDR_ENV_CARTPOLE at (4, 2, discrete), FDR_ENV_PENDULUM at
-// (3, 1, continuous), FDR_ENV_ACROBOT at (6, 3, discrete), FDR_ENV_MOUNTAINCAR at (2, 3, discrete),
-// FDR_ENV_MOUNTAINCAR_CONT at (2, 1, continuous); !WIDE only) -- per-lane reset states from the counter stream, each
-// env's termination test in its own branch (not kFeatTerm).
+// ENV: FDR_ENV_SYNTH, FDR_ENV_TRAP, or a physics env at its PhysicsSpec shape (fdr_internal.h; !WIDE only) -- per-lane
+// reset states from the counter stream, each env's termination test in PhysicsSim::step (not kFeatTerm).
+// Of the pieces shared with rollout_episodes_kernel (fdr_rollout_parts.h) the prologue, the draw batch, the discrete
+// selection and the Welford update keep their own text here: the synth / trap instances stay as is.
 // WIDE (synthetic env, few lanes: <= 2 waves per SIMD): a 256-VGPR budget instead of 128, so the
 // step's loop invariants (M / K rows, the head's W3 slice) stay in registers; the policy input and env
 // state cross lanes by v_readlane instead of an LDS round trip (NIN <= 8); a discrete env's candidate
@@ -163,13 +70,8 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
 
   const int ji = j < NIN ? j : NIN - 1;
   constexpr bool norm_obs = (FEAT & kFeatObsNorm) != 0;
-  const float om = norm_obs ? a.obs_mean[ji] : 0.f;
-  const float osd = norm_obs ? a.obs_std[ji] : 1.f;
-  auto policy_input = [&](float s) {
-    float x = s;
-    if (norm_obs) x = fminf(fmaxf((s - om) / osd, -10.f), 10.f);  // agent.py:40-41
-    return pl.input_transform(x);
-  };
+  const ObsInput<norm_obs> obs_input(a, ji);
+  auto policy_input = [&](float s) { return obs_input(pl, s); };
 
   int col = 0, row = 0;  // trap env state (wave-uniform)
   float s = 0.f;         // synthetic env state element j (j < NIN)
@@ -183,46 +85,13 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
   const int T = a.T;
   const uint64_t key = a.key;
   const uint64_t ulane = (uint64_t)(a.lanes.lane_offset + lane);  // global lane id
-  // physics env state (wave-uniform): CartPole (x, xdot, theta, thetadot); Pendulum (theta, thetadot, cos, sin);
-  // Acrobot (theta1, theta2, thetadot1, thetadot2); both MountainCars (position, velocity).
-  // Thread j < NIN selects observation element j into s, so everything downstream of s runs unchanged.
-  float px0 = 0.f, px1 = 0.f, px2 = 0.f, px3 = 0.f;
-  auto physics_obs = [&]() {
-    if constexpr (ENV == FDR_ENV_CARTPOLE) return j == 0 ? px0 : (j == 1 ? px1 : (j == 2 ? px2 : px3));
-    else if constexpr (ENV == FDR_ENV_ACROBOT) return acrobot_obs(j, px0, px1, px2, px3);
-    else if constexpr (ENV == FDR_ENV_MOUNTAINCAR || ENV == FDR_ENV_MOUNTAINCAR_CONT) return j == 0 ? px0 : px1;
-    else return j == 0 ? px2 : (j == 1 ? px3 : px1);
-  };
-  (void)physics_obs;
-  if constexpr (ENV == FDR_ENV_CARTPOLE) {  // gym: U(-0.05, 0.05) on all four
-    static_assert(NIN == 4 && NA == 2 && DISC && !WIDE, "CartPole: DiscretePolicy(4, 2), one-lane kernel");
-    px0 = physics_reset(key, ulane, 0, 0.1f, 0.05f);
-    px1 = physics_reset(key, ulane, 1, 0.1f, 0.05f);
-    px2 = physics_reset(key, ulane, 2, 0.1f, 0.05f);
-    px3 = physics_reset(key, ulane, 3, 0.1f, 0.05f);
-    s = physics_obs();
-  } else if constexpr (ENV == FDR_ENV_PENDULUM) {  // gym: theta ~ U(-pi, pi), thetadot ~ U(-1, 1)
-    static_assert(NIN == 3 && NA == 1 && !DISC && !WIDE, "Pendulum: MujocoPolicy(3, 1), one-lane kernel");
-    px0 = physics_reset(key, ulane, 0, kTwoPiF, kPiF);
-    px1 = physics_reset(key, ulane, 1, 2.f, 1.f);
-    px2 = cosf(px0);
-    px3 = sinf(px0);
-    s = physics_obs();
-  } else if constexpr (ENV == FDR_ENV_ACROBOT) {  // gym: U(-0.1, 0.1) on all four
-    static_assert(NIN == 6 && NA == 3 && DISC && !WIDE, "Acrobot: DiscretePolicy(6, 3), one-lane kernel");
-    px0 = physics_reset(key, ulane, 0, 0.2f, 0.1f);
-    px1 = physics_reset(key, ulane, 1, 0.2f, 0.1f);
-    px2 = physics_reset(key, ulane, 2, 0.2f, 0.1f);
-    px3 = physics_reset(key, ulane, 3, 0.2f, 0.1f);
-    s = physics_obs();
-  } else if constexpr (ENV == FDR_ENV_MOUNTAINCAR) {  // gym: position ~ U(-0.6, -0.4), at rest
-    static_assert(NIN == 2 && NA == 3 && DISC && !WIDE, "MountainCar: DiscretePolicy(2, 3), one-lane kernel");
-    px0 = physics_reset(key, ulane, 0, 0.2f, 0.6f);
-    s = physics_obs();
-  } else if constexpr (ENV == FDR_ENV_MOUNTAINCAR_CONT) {
-    static_assert(NIN == 2 && NA == 1 && !DISC && !WIDE, "MountainCarContinuous: MujocoPolicy(2, 1), one-lane kernel");
-    px0 = physics_reset(key, ulane, 0, 0.2f, 0.6f);
-    s = physics_obs();
+  constexpr bool kPhysics = ENV != FDR_ENV_SYNTH && ENV != FDR_ENV_TRAP;
+  [[maybe_unused]] PhysicsSim<ENV> sim;  // physics env state (wave-uniform)
+  if constexpr (kPhysics) {
+    static_assert(PhysicsSpec<ENV>::template is_shape<NIN, NA, DISC>() && !WIDE,
+                  "a physics env runs under its own policy shape, one-lane kernel");
+    sim.reset(key, ulane);
+    s = sim.obs(j);
   }
   constexpr bool kTerm = (FEAT & kFeatTerm) != 0;
   int nsteps = T;  // env.step calls of the episode (agent.py:47)
@@ -417,10 +286,7 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
           eacc -= (j < NA) ? disc_entropy_term(p, tot) : 0.f;
           }
         } else {
-          const float th = tanh_fast(y);
-          const float sd = std_from_tanh(dpp_mov<kDppRowShl + NA>(th));
-          eacc += __builtin_amdgcn_logf(sd);  // log2; lanes >= NA and the ln 2 scale: epilogue
-          act_c = kDet ? th : gauss_action(th, sd, zt);
+          act_c = gauss_head_action<NA, kDet>(y, zt, eacc);
         }
 
         mark(3, DISC ? (float)act_d : act_c);
@@ -448,44 +314,8 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
               return;
             }
           }
-        } else if constexpr (ENV == FDR_ENV_CARTPOLE) {
-          // reward 1 for every step taken, the failing one included; done after it (agent.py:46-52), or at T
-          const bool fail = cartpole_step(px0, px1, px2, px3, act_d);
-          racc += 1.0;
-          s = physics_obs();
-          if (__builtin_amdgcn_readfirstlane(fail ? 1 : 0)) {  // wave-uniform: the whole wave leaves its loop
-            nsteps = t + 1;
-            return;
-          }
-        } else if constexpr (ENV == FDR_ENV_PENDULUM) {
-          // the action (mean, or mean + std z, unscaled) sits in lane 0 of every row
-          racc += (double)pendulum_step(px0, px1, px2, px3, readlane_f(act_c, 0));
-          s = physics_obs();
-        } else if constexpr (ENV == FDR_ENV_ACROBOT) {
-          // reward -1 per step, 0 on the step that reaches the goal; done after it, or at T
-          const bool done = acrobot_step(px0, px1, px2, px3, act_d);
-          s = physics_obs();
-          if (__builtin_amdgcn_readfirstlane(done ? 1 : 0)) {
-            nsteps = t + 1;
-            return;
-          }
-          racc -= 1.0;
-        } else if constexpr (ENV == FDR_ENV_MOUNTAINCAR) {
-          // reward -1 for every step taken, the one that reaches the goal included
-          const bool done = mountaincar_step(px0, px1, (float)(act_d - 1) * 0.001f, 0.5f);
-          racc -= 1.0;
-          s = physics_obs();
-          if (__builtin_amdgcn_readfirstlane(done ? 1 : 0)) {
-            nsteps = t + 1;
-            return;
-          }
-        } else if constexpr (ENV == FDR_ENV_MOUNTAINCAR_CONT) {
-          // the force is the clamped action; the cost is the unclipped one's (gym), +100 on reaching the goal
-          const float ac = readlane_f(act_c, 0);
-          const bool done = mountaincar_step(px0, px1, fminf(fmaxf(ac, -1.f), 1.f) * 0.0015f, 0.45f);
-          racc += (double)((done ? 100.f : 0.f) - 0.1f * ac * ac);
-          s = physics_obs();
-          if (__builtin_amdgcn_readfirstlane(done ? 1 : 0)) {
+        } else if constexpr (kPhysics) {
+          if (sim.step(j, act_d, act_c, racc, s)) {
             nsteps = t + 1;
             return;
           }
@@ -515,17 +345,7 @@ __global__ __launch_bounds__(64 * kLanesPerBlock, WIDE ? 2 : 4) void rollout_ker
 #endif
 
   // ---- epilogue ----
-  eacc *= 0.693147180559945309f;  // log2 -> ln (both kinds)
-  const double esum = wave_sum((j < NA) ? (double)eacc : 0.0);
-  if (j == 0) {
-    double r = racc;
-    if (a.jiggle) r += (hash_ctr(key, ulane, kJiggleT, 15) & 1ull) ? 1e-12 : -1e-12;
-    a.ret[lane] = r;
-    double e = esum / (double)nsteps;  // mean over the visited states (agent.py:60-65)
-    if constexpr (!DISC) e += (double)NA * 1.4189385332046727;  // 0.5 + 0.5*ln(2*pi) per dim
-    a.ent[lane] = e;
-    a.steps[lane] = nsteps;
-  }
+  store_results<DISC>(a, lane, j, ulane, racc, entropy_sum(eacc, j, NA), nsteps, NA);
   if constexpr (FEAT & kFeatObsStats) {
     if (j < NIN) {
       a.os_mean[(int64_t)lane * NIN + j] = os_mean;

@@ -188,6 +188,21 @@ class RolloutResult(object):
         self.reward, self.entropy, self.timesteps, self.norm2 = ret, ent, steps, norm2
 
 
+def _rollout_outputs(n_lanes, dev):
+    """A RolloutResult whose four outputs share one allocation (one caching-allocator call per rollout)."""
+    buf = torch.empty(28 * n_lanes, dtype=torch.uint8, device=dev)
+    return RolloutResult(buf[:8 * n_lanes].view(torch.float64), buf[8 * n_lanes:16 * n_lanes].view(torch.float64),
+                         buf[24 * n_lanes:].view(torch.int32), buf[16 * n_lanes:24 * n_lanes].view(torch.float64))
+
+
+def _obs_stat_outputs(out, n_lanes, n_in, dev):
+    """The per-lane Welford obs statistics as out.obs_mean / obs_m2 / obs_count; -> the three tensors."""
+    out.obs_mean = torch.empty((n_lanes, n_in), dtype=torch.float32, device=dev)
+    out.obs_m2 = torch.empty_like(out.obs_mean)
+    out.obs_count = torch.empty(n_lanes, dtype=torch.int32, device=dev)
+    return out.obs_mean, out.obs_m2, out.obs_count
+
+
 def rollout(spec, env, lanes, n_lanes, seed, jiggle=True, obs_mean=None, obs_std=None,
             bn_mean=None, bn_var=None, out=None, device=None, states=None, obs_stats=None, ctx=None,
             u_inject=None):
@@ -197,10 +212,8 @@ def rollout(spec, env, lanes, n_lanes, seed, jiggle=True, obs_mean=None, obs_std
     normals for a continuous one) replacing the counter stream."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     _check_dev(obs_mean, obs_std, bn_mean, bn_var)
-    if out is None:  # the four outputs in one allocation (one caching-allocator call per rollout)
-        buf = torch.empty(28 * n_lanes, dtype=torch.uint8, device=dev)
-        out = RolloutResult(buf[:8 * n_lanes].view(torch.float64), buf[8 * n_lanes:16 * n_lanes].view(torch.float64),
-                            buf[24 * n_lanes:].view(torch.int32), buf[16 * n_lanes:24 * n_lanes].view(torch.float64))
+    if out is None:
+        out = _rollout_outputs(n_lanes, dev)
     pd = spec.desc(bn_mean, bn_var)
     ed = env.desc()
     if states is not None or obs_stats is not None or u_inject is not None:
@@ -219,13 +232,9 @@ def rollout(spec, env, lanes, n_lanes, seed, jiggle=True, obs_mean=None, obs_std
                 raise ValueError("states must be contiguous float32 [n_lanes, T, n_in]")
             x.states = states.data_ptr()
         if obs_stats is not None:
-            chance = float(obs_stats)
-            out.obs_mean = torch.empty((n_lanes, spec.n_in), dtype=torch.float32, device=dev)
-            out.obs_m2 = torch.empty_like(out.obs_mean)
-            out.obs_count = torch.empty(n_lanes, dtype=torch.int32, device=dev)
-            x.obs_mean, x.obs_m2, x.obs_count = out.obs_mean.data_ptr(), out.obs_m2.data_ptr(), \
-                out.obs_count.data_ptr()
-            x.obs_chance = chance
+            x.obs_chance = float(obs_stats)
+            x.obs_mean, x.obs_m2, x.obs_count = (t.data_ptr() for t in
+                                                 _obs_stat_outputs(out, n_lanes, spec.n_in, dev))
         check(lib.fdr_rollout_ex(_c(dev, ctx), ctypes.byref(pd), ctypes.byref(ed), ctypes.byref(lanes), n_lanes,
                                  ctypes.c_uint64(seed & ((1 << 64) - 1)), 1 if jiggle else 0, _p(obs_mean),
                                  _p(obs_std), _p(out.reward), _p(out.entropy), _p(out.timesteps),
@@ -254,9 +263,7 @@ def rollout_episodes(spec, env, lanes, n_lanes, seed, n_episodes, episode_ids=No
                 episode_ids.numel() != n_lanes * K:
             raise ValueError("episode_ids must be contiguous int64 [n_lanes, n_episodes]")
     if out is None:
-        buf = torch.empty(28 * n_lanes, dtype=torch.uint8, device=dev)
-        out = RolloutResult(buf[:8 * n_lanes].view(torch.float64), buf[8 * n_lanes:16 * n_lanes].view(torch.float64),
-                            buf[24 * n_lanes:].view(torch.int32), buf[16 * n_lanes:24 * n_lanes].view(torch.float64))
+        out = _rollout_outputs(n_lanes, dev)
     sq = None
     if ret_sq:
         sq = getattr(out, "reward_sq", None)
@@ -266,10 +273,8 @@ def rollout_episodes(spec, env, lanes, n_lanes, seed, n_episodes, episode_ids=No
     chance = 0.0
     if obs_stats is not None:
         chance = float(obs_stats)
-        om = out.obs_mean = torch.empty((n_lanes, spec.n_in), dtype=torch.float32, device=dev)
-        m2 = out.obs_m2 = torch.empty_like(om)
-        cnt = out.obs_count = torch.empty(n_lanes, dtype=torch.int32, device=dev)
-    pd = spec.desc(bn_mean, bn_var)
+        om, m2, cnt = _obs_stat_outputs(out, n_lanes, spec.n_in, dev)
+    pd =spec.desc(bn_mean, bn_var)
     ed = env.desc()
     check(lib.fdr_rollout_episodes(_c(dev, ctx), ctypes.byref(pd), ctypes.byref(ed), ctypes.byref(lanes), n_lanes,
                                    ctypes.c_uint64(seed & ((1 << 64) - 1)), 1 if jiggle else 0, _p(obs_mean),

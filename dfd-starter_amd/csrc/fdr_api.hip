@@ -992,7 +992,8 @@ int64_t fdr_atari_forward_workspace_bytes(int32_t n_act, int32_t n) {
 }
 
 int fdr_atari_env_frames(uint64_t env_seed, int64_t env_id, int32_t t0, int32_t n, float* frames, fdr_stream stream) {
-  if (n < 0 || t0 < 0 || t0 + (int64_t)n >= (1 << 20) || env_id < 0 || env_id >= (1ll << 31))
+  // the frame counter holds 32 bits of env id (gid << 32): every id a rollout's lane_offset can reach below 2^32
+  if (n < 0 || t0 < 0 || t0 + (int64_t)n >= (1 << 20) || env_id < 0 || env_id >= (1ll << 32))
     return set_error(FDR_ERR_INVALID, "bad range");
   if (n > 0 && !frames) return set_error(FDR_ERR_INVALID, "NULL frames");
   return atari::launch_env_frames(env_seed, (uint64_t)env_id, t0, n, frames, (hipStream_t)stream);

@@ -96,10 +96,14 @@ __global__ __launch_bounds__(256) void stats_kernel(const float* __restrict__ X,
 
 // torch CPU train-mode BN (double accumulation): mean, var_sum; invstd = 1 / sqrt(var_sum / N + eps);
 // running_mean = m * mean + (1 - m) * rm, running_var = m * var_sum / (N - 1) + (1 - m) * rv
+// center != NULL (AtariPolicy): the centred form y = (x - center) scale + shift with center = mean, shift = bias, in
+// place of y = x scale + (bias - mean scale).  Atari's BNs follow convs of raw 0..255 pixels: x scale is ~1e4 against
+// a result of O(1), and with a batch variance near 0 (scale = w / sqrt(eps)) the uncentred sum leaves a residue of
+// ~1e-3 of the bias; x - mean is exact there.
 __global__ void finalize_kernel(int C, int nb, int64_t N, const double* __restrict__ part,
                                 const float* __restrict__ w, const float* __restrict__ bias, float momentum,
                                 float* __restrict__ rm, float* __restrict__ rv, float* __restrict__ scale,
-                                float* __restrict__ shift) {
+                                float* __restrict__ shift, float* __restrict__ center) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   double s = 0.0, q = 0.0;
@@ -113,7 +117,12 @@ __global__ void finalize_kernel(int C, int nb, int64_t N, const double* __restri
   const float invstd = (float)(1.0 / sqrt(var_sum / (double)N + (double)kBnEps));
   const float alpha = invstd * w[c];
   scale[c] = alpha;
-  shift[c] = bias[c] - (float)mean * alpha;
+  if (center) {
+    center[c] = (float)mean;
+    shift[c] = bias[c];
+  } else {
+    shift[c] = bias[c] - (float)mean * alpha;
+  }
   const double m = (double)momentum;
   rm[c] = (float)(m * mean + (1.0 - m) * (double)rm[c]);
   rv[c] = (float)(m * (var_sum / (double)(N - 1)) + (1.0 - m) * (double)rv[c]);
@@ -361,7 +370,7 @@ int launch_vbn(const VbnCall& a, void* ws, int64_t ws_bytes, hipStream_t s) {
     hipLaunchKernelGGL(stats_kernel, dim3(C, nb), dim3(256), 0, s, in, n, C, HW, relu, div, part);
     const float* w = th + P.bn_w[k];
     hipLaunchKernelGGL(finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, C, nb, (int64_t)n * HW, part, w,
-                       w + C, a.momentum, a.bn_mean + L.bn_stat[k], a.bn_var + L.bn_stat[k], sc, sh);
+                       w + C, a.momentum, a.bn_mean + L.bn_stat[k], a.bn_var + L.bn_stat[k], sc, sh, (float*)nullptr);
   };
   auto pool = [&](const float* in, int C, int H, float* out) {
     const int64_t total = (int64_t)n * C * (H / 2) * (H / 2);
@@ -436,11 +445,13 @@ constexpr int64_t kC1w = 0, kC1b = kC1w + kA1 * 4 * 64, kBn1 = kC1b + kA1, kC2w 
                   kFcb = kFcw + (int64_t)kAFc * kAFeat, kBn3 = kFcb + kAFc;
 
 // Y[i][co][oy][ox] = b[co] + sum_{ci,ky,kx} W[co][ci][ky][kx] * act(X[i][ci][S oy + ky][S ox + kx])  (no padding);
-// act = relu(scale[ci] x + shift[ci]) (the previous layer's train-mode BN) when BNIN, else the raw input
+// act = relu((x - center[ci]) scale[ci] + shift[ci]) (the previous layer's train-mode BN, centred: finalize_kernel) when
+// BNIN, else the raw input
 template <int CIN, int COUT, int K, int S, int HI, int HO, bool BNIN>
 __global__ __launch_bounds__(256) void sconv_kernel(const float* __restrict__ X, const float* __restrict__ scale,
-                                                    const float* __restrict__ shift, const float* __restrict__ W,
-                                                    const float* __restrict__ b, float* __restrict__ Y, int64_t total) {
+                                                    const float* __restrict__ shift, const float* __restrict__ center,
+                                                    const float* __restrict__ W, const float* __restrict__ b,
+                                                    float* __restrict__ Y, int64_t total) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
   const int ox = (int)(e % HO), oy = (int)((e / HO) % HO), co = (int)((e / (HO * HO)) % COUT);
@@ -449,13 +460,13 @@ __global__ __launch_bounds__(256) void sconv_kernel(const float* __restrict__ X,
   for (int ci = 0; ci < CIN; ++ci) {
     const float* xp = X + ((i * CIN + ci) * HI + S * oy) * HI + S * ox;
     const float* wp = W + ((int64_t)co * CIN + ci) * K * K;
-    const float sc = BNIN ? scale[ci] : 1.f, sh = BNIN ? shift[ci] : 0.f;
+    const float sc = BNIN ? scale[ci] : 1.f, sh = BNIN ? shift[ci] : 0.f, mu = BNIN ? center[ci] : 0.f;
 #pragma unroll
     for (int ky = 0; ky < K; ++ky)
 #pragma unroll
       for (int kx = 0; kx < K; ++kx) {
         float v = xp[ky * HI + kx];
-        if (BNIN) v = fmaxf(fmaf(v, sc, sh), 0.f);
+        if (BNIN) v = fmaxf(fmaf(v - mu, sc, sh), 0.f);
         acc = fmaf(wp[ky * K + kx], v, acc);
       }
   }
@@ -464,13 +475,14 @@ __global__ __launch_bounds__(256) void sconv_kernel(const float* __restrict__ X,
 
 // F[i][o] = fc_b[o] + sum_k fc_w[o][k] relu(BN2d(X2))[i][k]  (k = c * 81 + p: the C, H, W flatten of atari.py:47)
 __global__ __launch_bounds__(256) void afc_kernel(const float* __restrict__ X, int n, const float* __restrict__ scale,
-                                                  const float* __restrict__ shift, const float* __restrict__ WT,
-                                                  const float* __restrict__ b, float* __restrict__ F) {
+                                                  const float* __restrict__ shift, const float* __restrict__ center,
+                                                  const float* __restrict__ WT, const float* __restrict__ b,
+                                                  float* __restrict__ F) {
   __shared__ float xs[kFcRows][kAFeat];
   const int i0 = blockIdx.x * kFcRows, tid = threadIdx.x;
   for (int e = tid; e < kFcRows * kAFeat; e += 256) {
     const int r = e / kAFeat, k = e % kAFeat, c = k / (kO2 * kO2);
-    xs[r][k] = i0 + r < n ? fmaxf(fmaf(X[(int64_t)(i0 + r) * kAFeat + k], scale[c], shift[c]), 0.f) : 0.f;
+    xs[r][k] = i0 + r < n ? fmaxf(fmaf(X[(int64_t)(i0 + r) * kAFeat + k] - center[c], scale[c], shift[c]), 0.f) : 0.f;
   }
   __syncthreads();
   float acc[kFcRows];
@@ -485,7 +497,7 @@ __global__ __launch_bounds__(256) void afc_kernel(const float* __restrict__ X, i
 }
 
 struct AVbnPlan {
-  int64_t X1, X2, F, WT, part, scale, shift, total;
+  int64_t X1, X2, F, WT, part, scale, shift, center, total;
 };
 
 AVbnPlan avbn_plan(int n) {
@@ -498,6 +510,7 @@ AVbnPlan avbn_plan(int n) {
   p.part = ws.take((int64_t)kAFc * impala::kStatBlocks * 2 * 8);
   p.scale = ws.take((int64_t)kAFc * 4);
   p.shift = ws.take((int64_t)kAFc * 4);
+  p.center = ws.take((int64_t)kAFc * 4);
   p.total = ws.used;
   return p;
 }
@@ -518,24 +531,25 @@ int launch_vbn(const VbnCall& c, void* ws, int64_t ws_bytes, hipStream_t s) {
   double* part = reinterpret_cast<double*>(base + pl.part);
   float* sc = reinterpret_cast<float*>(base + pl.scale);
   float* sh = reinterpret_cast<float*>(base + pl.shift);
+  float* mu = reinterpret_cast<float*>(base + pl.center);
   const float* th = c.theta;
   const int nb = n < impala::kStatBlocks ? n : impala::kStatBlocks;
   // statistics of a BN's input [n][C][HW] -> its running stats (at `at` in the flat [16 | 32 | 256]) + sc / sh
   auto bn_stats = [&](const float* in, int C, int HW, int64_t w, int at) {
     hipLaunchKernelGGL(stats_kernel, dim3(C, nb), dim3(256), 0, s, in, n, C, HW, 0, 1.f, part);
     hipLaunchKernelGGL(finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, C, nb, (int64_t)n * HW, part, th + w,
-                       th + w + C, c.momentum, c.bn_mean + at, c.bn_var + at, sc, sh);
+                       th + w + C, c.momentum, c.bn_mean + at, c.bn_var + at, sc, sh, mu);
   };
   auto grid = [](int64_t total) { return dim3((unsigned)((total + 255) / 256)); };
   const int64_t t1 = (int64_t)n * kA1 * kO1 * kO1, t2 = (int64_t)n * kAFeat;
   hipLaunchKernelGGL((sconv_kernel<4, kA1, 8, 4, 84, kO1, false>), grid(t1), dim3(256), 0, s, c.frames, nullptr,
-                     nullptr, th + kC1w, th + kC1b, X1, t1);
+                     nullptr, nullptr, th + kC1w, th + kC1b, X1, t1);
   bn_stats(X1, kA1, kO1 * kO1, kBn1, 0);
-  hipLaunchKernelGGL((sconv_kernel<kA1, kA2, 4, 2, kO1, kO2, true>), grid(t2), dim3(256), 0, s, X1, sc, sh, th + kC2w,
-                     th + kC2b, X2, t2);
+  hipLaunchKernelGGL((sconv_kernel<kA1, kA2, 4, 2, kO1, kO2, true>), grid(t2), dim3(256), 0, s, X1, sc, sh, mu,
+                     th + kC2w, th + kC2b, X2, t2);
   bn_stats(X2, kA2, kO2 * kO2, kBn2, kA1);
   hipLaunchKernelGGL(transpose_kernel, dim3(kAFc * kAFeat / 256), dim3(256), 0, s, th + kFcw, kAFc, kAFeat, WT);
-  hipLaunchKernelGGL(afc_kernel, dim3((n + kFcRows - 1) / kFcRows), dim3(256), 0, s, X2, n, sc, sh, WT, th + kFcb, F);
+  hipLaunchKernelGGL(afc_kernel, dim3((n + kFcRows - 1) / kFcRows), dim3(256), 0, s, X2, n, sc, sh, mu, WT, th + kFcb, F);
   bn_stats(F, kAFc, 1, kBn3, kA1 + kA2);
   return check_launch("atari bn refresh");
 }

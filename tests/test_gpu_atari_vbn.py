@@ -90,3 +90,75 @@ def test_compute_vbn_rejects_a_single_frame():
         engine.check(engine.lib.fdr_atari_bn_refresh(None, ctypes.byref(d), engine._p(pol.flat), 1, engine._p(fr), 0.1,
                                                      engine._p(bm), engine._p(bv), engine._p(ws), ws.numel(), None),
                      "fdr_atari_bn_refresh")
+
+
+# ---- edges, against the float64 restatement (tests/atari_ref.py); the _check rule above, not a wider one -------------
+def _edge_inputs(A=7):
+    import atari_cases as ac
+    rs = np.random.RandomState(5)
+    flat = ac.make_theta(A, 1)   # every section distinct and O(1): biases, BN weights of mixed sign with one exact 0
+    rm = (rs.randn(304) * 5).astype(np.float32)
+    rv = (1.0 + rs.rand(304) * 20).astype(np.float32)
+    return A, flat, rm, rv
+
+
+@pytest.mark.parametrize("n", [2, 8, 9, 64, 65])
+def test_compute_vbn_buffer_sizes_vs_float64(n):
+    """n = 2: the smallest legal buffer; 8 / 9 straddle the fc kernel's 8-row blocks; 64 / 65 the 64 statistic blocks
+    (at 65 each block takes 2 samples and the trailing blocks are empty)."""
+    import atari_ref as ar
+    A, flat, rm, rv = _edge_inputs()
+    frames = np.random.RandomState(n).randint(0, 256, size=(n, 4, 84, 84)).astype(np.float32)
+    pol, _ = _policy(A, flat, rm, rv)
+    pol.compute_vbn(frames)
+    torch.cuda.synchronize()
+    want_rm, want_rv = ar.compute_vbn(ar.unflatten(flat, A), rm, rv, frames, 0.1)
+    _check(pol, want_rm, want_rv, "n%d" % n)
+
+
+@pytest.mark.parametrize("value", [0.0, 37.0, 255.0])
+def test_compute_vbn_constant_buffer(value):
+    """Every frame the same constant: every batch variance is exactly 0, so rv_new = (1 - m) rv exactly (the var_sum
+    clamp and the 1 / sqrt(eps) scale), rm_new follows the conv bias chain (conv1 = v sum(w) + b -> BN2d gives its
+    bias -> conv2 of relu(bias) -> ...), and nothing is non-finite."""
+    import atari_ref as ar
+    A, flat, rm, rv = _edge_inputs()
+    frames = np.full((5, 4, 84, 84), value, np.float32)
+    pol, _ = _policy(A, flat, rm, rv)
+    pol.compute_vbn(frames)
+    torch.cuda.synchronize()
+    bm, bv = pol.bn_stats()
+    bm, bv = bm.cpu().numpy(), bv.cpu().numpy()
+    assert np.isfinite(bm).all() and np.isfinite(bv).all()
+    m = float(np.float32(0.1))
+    np.testing.assert_array_equal(bv, ((1.0 - m) * rv.astype(np.float64)).astype(np.float32))
+    want_rm, want_rv = ar.compute_vbn(ar.unflatten(flat, A), rm, rv, frames, 0.1)
+    _check(pol, want_rm, want_rv, "const%g" % value)
+
+
+def test_compute_vbn_momentum_zero_and_one():
+    """momentum 0: the stats are bitwise unchanged; momentum 1: they are the batch statistics alone, whatever they
+    were (two different starting points give the same bits)."""
+    import atari_ref as ar
+    from fdr import engine
+    A, flat, rm, rv = _edge_inputs()
+    frames = torch.as_tensor(np.random.RandomState(11).randint(0, 256, size=(9, 4, 84, 84)).astype(np.float32),
+                             device="cuda")
+    spec = engine.AtariSpec(A)
+    th = torch.as_tensor(flat, device="cuda")
+
+    def run(m0, v0, momentum):
+        bm, bv = torch.as_tensor(m0, device="cuda").clone(), torch.as_tensor(v0, device="cuda").clone()
+        engine.atari_bn_refresh(spec, th, frames, bm, bv, momentum)
+        torch.cuda.synchronize()
+        return bm.cpu().numpy(), bv.cpu().numpy()
+    bm, bv = run(rm, rv, 0.0)
+    assert bm.tobytes() == rm.tobytes() and bv.tobytes() == rv.tobytes()
+    bm, bv = run(rm, rv, 1.0)
+    bm2, bv2 = run(np.zeros(304, np.float32), np.ones(304, np.float32), 1.0)
+    assert bm.tobytes() == bm2.tobytes() and bv.tobytes() == bv2.tobytes()
+    want_rm, want_rv = ar.compute_vbn(ar.unflatten(flat, A), rm, rv, frames.cpu().numpy(), 1.0)
+    for got, want, name in ((bm, want_rm, "rm"), (bv, want_rv, "rv")):
+        for lo, hi in ((0, 16), (16, 48), (48, 304)):
+            floor = 1e-6 * max(1.0, float(np.abs(want[lo:hi]).max()))
+            np.testing.assert_allclose(got[lo:hi], want[lo:hi], rtol=RTOL, atol=floor, err_msg="m1 %s [%d:%d]" % (name, lo, hi))

@@ -865,7 +865,9 @@ int fdr_impala_strategies(fdr_ctx* ctx, const fdr_impala_desc* d, const fdr_lane
 int fdr_impala_env_frames(uint64_t env_seed, int32_t n_act, int64_t env_id, int32_t t0, int32_t n,
                           const int32_t* actions, float* frames, float* reward, fdr_stream stream) {
   if (n_act < 1 || n_act > impala::kMaxAct) return set_error(FDR_ERR_INVALID, "n_act must be in 1..32");
-  if (n < 0 || t0 < 0 || t0 + (int64_t)n >= (1 << 20) || env_id < 0) return set_error(FDR_ERR_INVALID, "bad range");
+  // the frame counter holds 32 bits of env id (gid << 32): a larger id would alias another env's frames
+  if (n < 0 || t0 < 0 || t0 + (int64_t)n >= (1 << 20) || env_id < 0 || env_id >= (1ll << 32))
+    return set_error(FDR_ERR_INVALID, "bad range");
   if (n > 0 && !frames) return set_error(FDR_ERR_INVALID, "NULL frames");
   return impala::launch_env_frames(env_seed, n_act, (uint64_t)env_id, t0, n, actions, frames, reward,
                                    (hipStream_t)stream);

@@ -527,6 +527,9 @@ int64_t fdr_impala_num_bn_stats(void);
  *   ret, ent (f64), steps (i32) per env; norm2 [n_lanes] f64 per lane;
  *   actions [n_lanes*E, T] i32 and probs [n_lanes*E, T, A] f32 optional (NULL) per-step traces.
  * workspace: fdr_impala_workspace_bytes(desc, n_lanes) bytes (theta' packs + per-step state).
+ * Precondition (not checked, as for fdr_rollout): the global env ids (lanes->lane_offset + l) * E + e lie in
+ * [0, 2^32) -- the frame, reward and action counters hold 32 id bits (id << 32), so an id beyond them runs as
+ * id mod 2^32 (the oracle's counter wraps the same way), which is another env's stream.
  * Replaces Worker.collect_returns with an ImpalaPolicy (worker/worker.py:20-38). */
 int64_t fdr_impala_workspace_bytes(const fdr_impala_desc* desc, int32_t n_lanes);
 int fdr_impala_rollout(fdr_ctx* ctx, const fdr_impala_desc* desc, const fdr_lanes_desc* lanes,
@@ -630,7 +633,8 @@ int fdr_impala_bn_refresh(fdr_ctx* ctx, const fdr_impala_desc* desc, const float
 
 /* Observations of the synthetic frame env outside a rollout (eval states and the probe set zeta,
  * run_sequential.py:142-143, 198-213): frames [n, 3, 64, 64] f32 (0..255) of global env `env_id`
- * (= lane_offset * E + lane * E + e of a rollout) at steps t0 .. t0+n-1, and -- given the actions [n] i32
+ * (= lane_offset * E + lane * E + e of a rollout, 0 <= env_id < 2^32: the counter's 32 id bits; any other id is
+ * FDR_ERR_INVALID, nothing written) at steps t0 .. t0+n-1 < 2^20 - 1, and -- given the actions [n] i32
  * taken at those steps (NULL -> 0) -- reward [n] f32 (nullable) that each step returns. */
 int fdr_impala_env_frames(uint64_t env_seed, int32_t n_act, int64_t env_id, int32_t t0, int32_t n,
                           const int32_t* actions, float* frames, float* reward, fdr_stream stream);

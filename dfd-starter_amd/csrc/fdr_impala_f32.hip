@@ -1,17 +1,15 @@
 // fdr_impala_f32.hip -- ImpalaPolicy device code in f32: the conv stack, the LSTM core step in its per-lane, pair and
 // pair-replay forms, and the two row GEMMs (entropy replay input projection, get_strategy fc).  The GEMMs' HALF
 // instances read the half pack but are the same template.  Launched from fdr_impala.hip; declarations:
-// fdr_impala_kernels.h.
+// fdr_impala_kernels.h; the core step's shared phases: fdr_impala_core.h.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 
-#include "fdr_impala_kernels.h"
+#include "fdr_impala_core.h"
 
 namespace fdr {
 namespace impala {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------
 // conv stack: one workgroup (8 waves) per (lane, env); everything between the frame and the
@@ -407,9 +405,8 @@ __global__ __launch_bounds__(kConvThreads) void conv_kernel(Layout L, StepArgs a
 // core: one workgroup (256 threads) per lane, E envs.  Thread j owns fc unit j and LSTM unit j
 // (gate rows j, 256+j, 512+j, 768+j), so the cell update is thread-local; weights stream from the
 // pack as coalesced rows of W^T, activations are LDS broadcasts.
+// The phases every core form shares (cell, BN1d fold, head, pair operands, core-input rows): fdr_impala_core.h.
 // ------------------------------------------------------------------------------------------
-
-
 template <int E, int MODE>
 __global__ __launch_bounds__(kCoreThreads) void core_kernel(Layout L, StepArgs a) {
   // xw: the BN'd features xs [2048][E] during the fc, then the fc partial sums [4][256][E] (first
@@ -428,17 +425,15 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel(Layout L, StepArgs a
   const int c4 = j & 63, wq = j >> 6;  // float4 column group, wave index
 
   if constexpr (!seq_mode(MODE)) {
+    // ---- BN1d(features) -> xs ----
     for (int k = j; k < kFeat; k += kCoreThreads) {
-      const float rmv = (a.bn_mean ? a.bn_mean + L.bn_stat[15] : a.pack)[k];  // branch-free
-      const float rvv = (a.bn_var ? a.bn_var + L.bn_stat[15] : a.pack)[k];
-      const float rm = a.bn_mean ? rmv : 0.f, rv = a.bn_var ? rvv : 1.f;
-      const float sc = pk[L.bn_w[15] + k] * (1.f / sqrtf(rv + kBnEps));
-      const float sh = fmaf(-rm, sc, pk[L.bn_b[15] + k]);
+      float sc, sh;
+      bn1d_fold(L, pk, 15, k, bn1d_stats(L, a, 15, k, a.pack), sc, sh);
 #pragma unroll
       for (int e = 0; e < E; ++e) xw[k * E + e] = fmaf(a.feat[(e0 + e) * kFeat + k], sc, sh);
     }
     __syncthreads();
-    // fc (2048 -> 256): wave wq streams rows [512 wq, 512 wq + 512) of W^T as float4 (1 KiB / wave-load)
+    // ---- fc (2048 -> 256): wave wq streams rows [512 wq, 512 wq + 512) of W^T as float4 (1 KiB / wave-load) ----
     float acc[4][E];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -463,6 +458,7 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel(Layout L, StepArgs a
 #pragma unroll
       for (int e = 0; e < E; ++e) xw[(wq * kHid + 4 * c4 + c) * E + e] = acc[c][e];
     __syncthreads();
+    // ---- core input [relu(fc) | clip(r)] ----
     const float bj = pk[L.fc_b + j];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -475,30 +471,17 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel(Layout L, StepArgs a
     }
     if (MODE == kRollout && a.ci) {
       __syncthreads();
-      float* dst = a.ci + ((int64_t)a.t * a.n_lanes * E + e0) * kCoreIn;
-      for (int i = j; i < kCoreIn * E; i += kCoreThreads) {
-        const int e = i / kCoreIn, k = i - e * kCoreIn;
-        dst[i] = cis[k * E + e];
-      }
+      store_ci_rows<E>(ci_step<E>(a, e0), cis);
     }
   } else if (!a.gx) {
-    const float* src = a.ci + ((int64_t)a.t * a.n_lanes * E + e0) * kCoreIn;
-    for (int i = j; i < kCoreIn * E; i += kCoreThreads) {
-      const int e = i / kCoreIn, k = i - e * kCoreIn;
-      cis[k * E + e] = src[i];
-    }
+    load_ci_rows<E>(ci_step<E>(a, e0), cis);
   }
   float cj[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const float nd = (MODE == kForward && a.notdone) ? a.notdone[e0 + e] : 1.f;
-    hs[j * E + e] = nd * a.h[(e0 + e) * kHid + j];
-    cj[e] = nd * a.c[(e0 + e) * kHid + j];
-  }
+  load_state<E, MODE>(a, e0, j, hs, cj);
   __syncthreads();
 
-  // LSTM gates (torch order i, f, g, o): thread j streams columns 4j .. 4j+3 of [W_ih | W_hh]^T, so
-  // wave wq computes gate wq; gates = (W_ih x + b_ih) + (W_hh h + b_hh)
+  // ---- LSTM gates (torch order i, f, g, o): thread j streams columns 4j .. 4j+3 of [W_ih | W_hh]^T, so
+  // wave wq computes gate wq; gates = (W_ih x + b_ih) + (W_hh h + b_hh) ----
   {
     float ax[4][E], ah[4][E];
 #pragma unroll
@@ -551,35 +534,23 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel(Layout L, StepArgs a
       for (int e = 0; e < E; ++e) xw[(4 * j + c) * E + e] = (ax[c][e] + bif[c]) + (ah[c][e] + bhf[c]);
   }
   __syncthreads();  // gates complete; all reads of the old h are done
+  // ---- cell, BN1d(h'), head ----
   float hj[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {
-    const float gi = sigm(xw[j * E + e]);
-    const float gf = sigm(xw[(kHid + j) * E + e]);
-    const float gg = tanhf(xw[(2 * kHid + j) * E + e]);
-    const float go = sigm(xw[(3 * kHid + j) * E + e]);
-    cj[e] = fmaf(gf, cj[e], gi * gg);  // explicit: the same rounding in every core form
-    hj[e] = go * tanhf(cj[e]);
+    const float pre[4] = {xw[j * E + e], xw[(kHid + j) * E + e], xw[(2 * kHid + j) * E + e], xw[(3 * kHid + j) * E + e]};
+    hj[e] = lstm_cell<false>(pre, cj[e]);
     a.h[(e0 + e) * kHid + j] = hj[e];
     a.c[(e0 + e) * kHid + j] = cj[e];
   }
   {
-    const float rmv = (a.bn_mean ? a.bn_mean + L.bn_stat[16] : pk)[j];  // branch-free (see conv_kernel's table)
-    const float rvv = (a.bn_var ? a.bn_var + L.bn_stat[16] : pk)[j];
-    const float rm = a.bn_mean ? rmv : 0.f, rv = a.bn_var ? rvv : 1.f;
-    const float sc = pk[L.bn_w[16] + j] * (1.f / sqrtf(rv + kBnEps));
-    const float sh = fmaf(-rm, sc, pk[L.bn_b[16] + j]);
+    float sc, sh;
+    bn1d_fold(L, pk, 16, j, bn1d_stats(L, a, 16, j, pk), sc, sh);
 #pragma unroll
     for (int e = 0; e < E; ++e) hs[j * E + e] = fmaf(hj[e], sc, sh);
   }
   __syncthreads();
-  if (j < A * E) {  // policy head Linear(256 -> A) (policies/impala.py:122, 184)
-    const int ai = j / E, e = j - ai * E;
-    const float* w = pk + L.head_w + ai * kHid;
-    float s = 0.f;
-    for (int k = 0; k < kHid; ++k) s = fmaf(w[k], hs[k * E + e], s);
-    logit[e * kMaxAct + ai] = s + pk[L.head_b + ai];
-  }
+  head_rows<E, E>(pk, pk, L, A, hs, logit);
   __syncthreads();
   if (j < E) core_finish<E, MODE>(a, logit, lane, j);
 }
@@ -591,6 +562,7 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel(Layout L, StepArgs a
 // L2 / MALL) and forms w = fl32(theta + s_l E) in registers -- the per-lane pack's value bit for bit (an fma
 // with s = +-1 rounds theta +- E once), so every env sees core_kernel's exact fma chains; half its HBM bytes.
 // The pair's 2E envs are contiguous, biases / BN / head are each lane's own pack.
+// Pair operands, gate biases, cell, BN1d fold and head: fdr_impala_core.h.
 // ------------------------------------------------------------------------------------------
 template <int E>
 __global__ __launch_bounds__(kCoreThreads) void core_kernel_p(Layout L, StepArgs a) {
@@ -613,20 +585,9 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel_p(Layout L, StepArgs
   const int A = a.n_act;
   const int c4 = j & 63, wq = j >> 6;
   auto pkof = [&](int e) { return e < E ? pk0 : pk1; };
-  // one streamed float4 row: w = fl32(theta + s_l E) per lane, then each env's fma chain of core_kernel
-  auto accum = [&](float (&acc)[4][E2], float4 t, float4 d, const float* x) {
-    const float tp[4] = {fmaf(sg0, d.x, t.x), fmaf(sg0, d.y, t.y), fmaf(sg0, d.z, t.z), fmaf(sg0, d.w, t.w)};
-    const float tm[4] = {fmaf(sg1, d.x, t.x), fmaf(sg1, d.y, t.y), fmaf(sg1, d.z, t.z), fmaf(sg1, d.w, t.w)};
-#pragma unroll
-    for (int e = 0; e < E2; ++e) {
-      const float xv = x[e];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c][e] = fmaf(e < E ? tp[c] : tm[c], xv, acc[c][e]);
-    }
-  };
+  const PairF32<E> P{pk0, pk1, ep, sg0, sg1};
 
-  // branch-free BN1d loads (a conditional load ends its block with a full vmcnt wait; without running
-  // statistics the loads read the pack and the values are replaced by 0 / 1) -- the same values
+  // the statistics once per element (branch-free, as FDR_BN1D_STATS), the fold per lane
   const bool has_m = a.bn_mean != nullptr, has_v = a.bn_var != nullptr;
   const float* bmp = has_m ? a.bn_mean + L.bn_stat[15] : pk0;
   const float* bvp = has_v ? a.bn_var + L.bn_stat[15] : pk0;
@@ -638,8 +599,8 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel_p(Layout L, StepArgs
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       const float* pk = hf ? pk1 : pk0;
-      const float sc = pk[L.bn_w[15] + k] * (1.f / sqrtf(rv + kBnEps));
-      const float sh = fmaf(-rm, sc, pk[L.bn_b[15] + k]);
+      float sc, sh;
+      FDR_BN1D_FOLD(pk[L.bn_w[15] + k], pk[L.bn_b[15] + k], rm, rv, sc, sh)
 #pragma unroll
       for (int e = 0; e < E; ++e) xw[k * E2 + hf * E + e] = fmaf(a.feat[(e0 + hf * E + e) * kFeat + k], sc, sh);
     }
@@ -655,7 +616,7 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel_p(Layout L, StepArgs
     const float4* d4 = reinterpret_cast<const float4*>(ep + L.fc_wt) + c4;
 #pragma unroll FDR_CORE_UNROLL
     for (int k = wq * (kFeat / 4); k < (wq + 1) * (kFeat / 4); ++k)
-      accum(acc, t4[(int64_t)k * (kHid / 4)], ld_stream(d4 + (int64_t)k * (kHid / 4)), xw + k * E2);
+      P.accum(acc, t4[(int64_t)k * (kHid / 4)], ld_stream(d4 + (int64_t)k * (kHid / 4)), xw + k * E2);
     __syncthreads();  // xs is dead
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -695,56 +656,37 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel_p(Layout L, StepArgs
     const float4* dl = reinterpret_cast<const float4*>(ep + L.lstm_wt) + j;
 #pragma unroll FDR_CORE_UNROLL
     for (int k = 0; k < kCoreIn; ++k)
-      accum(ax, tl[(int64_t)k * (kGates / 4)], ld_stream(dl + (int64_t)k * (kGates / 4)), cis + k * E2);
+      P.accum(ax, tl[(int64_t)k * (kGates / 4)], ld_stream(dl + (int64_t)k * (kGates / 4)), cis + k * E2);
 #pragma unroll FDR_CORE_UNROLL
     for (int k = 0; k < kHid; ++k)
-      accum(ah, tl[(int64_t)(kCoreIn + k) * (kGates / 4)], ld_stream(dl + (int64_t)(kCoreIn + k) * (kGates / 4)),
+      P.accum(ah, tl[(int64_t)(kCoreIn + k) * (kGates / 4)], ld_stream(dl + (int64_t)(kCoreIn + k) * (kGates / 4)),
             hs + k * E2);
-    const float4 bi0 = reinterpret_cast<const float4*>(pk0 + L.lstm_bih)[j];
-    const float4 bh0 = reinterpret_cast<const float4*>(pk0 + L.lstm_bhh)[j];
-    const float4 bi1 = reinterpret_cast<const float4*>(pk1 + L.lstm_bih)[j];
-    const float4 bh1 = reinterpret_cast<const float4*>(pk1 + L.lstm_bhh)[j];
-    const float bif0[4] = {bi0.x, bi0.y, bi0.z, bi0.w}, bhf0[4] = {bh0.x, bh0.y, bh0.z, bh0.w};
-    const float bif1[4] = {bi1.x, bi1.y, bi1.z, bi1.w}, bhf1[4] = {bh1.x, bh1.y, bh1.z, bh1.w};
+    const auto gb = P.gate_bias(L, j);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int e = 0; e < E2; ++e)
-        xw[(4 * j + c) * E2 + e] = (ax[c][e] + (e < E ? bif0[c] : bif1[c])) + (ah[c][e] + (e < E ? bhf0[c] : bhf1[c]));
+      for (int e = 0; e < E2; ++e) xw[(4 * j + c) * E2 + e] = P.gate_pre(gb, c, e, ax[c][e], ah[c][e]);
   }
   __syncthreads();
   float hj[E2];
 #pragma unroll
   for (int e = 0; e < E2; ++e) {
-    const float gi = sigm(xw[j * E2 + e]);
-    const float gf = sigm(xw[(kHid + j) * E2 + e]);
-    const float gg = tanhf(xw[(2 * kHid + j) * E2 + e]);
-    const float go = sigm(xw[(3 * kHid + j) * E2 + e]);
-    cj[e] = fmaf(gf, cj[e], gi * gg);  // explicit: the same rounding in every core form
-    hj[e] = go * tanhf(cj[e]);
+    FDR_LSTM_CELL(sigm, tanhf, xw[j * E2 + e], xw[(kHid + j) * E2 + e], xw[(2 * kHid + j) * E2 + e],
+                  xw[(3 * kHid + j) * E2 + e], cj[e], hj[e])
     a.h[(e0 + e) * kHid + j] = hj[e];
     a.c[(e0 + e) * kHid + j] = cj[e];
   }
 #pragma unroll
   for (int hf = 0; hf < 2; ++hf) {
     const float* pk = hf ? pk1 : pk0;
-    const float rmv = (a.bn_mean ? a.bn_mean + L.bn_stat[16] : pk)[j];  // branch-free (see conv_kernel's table)
-    const float rvv = (a.bn_var ? a.bn_var + L.bn_stat[16] : pk)[j];
-    const float rm = a.bn_mean ? rmv : 0.f, rv = a.bn_var ? rvv : 1.f;
-    const float sc = pk[L.bn_w[16] + j] * (1.f / sqrtf(rv + kBnEps));
-    const float sh = fmaf(-rm, sc, pk[L.bn_b[16] + j]);
+    FDR_BN1D_STATS(16, j, pk, rm, rv)
+    float sc, sh;
+    FDR_BN1D_FOLD(pk[L.bn_w[16] + j], pk[L.bn_b[16] + j], rm, rv, sc, sh)
 #pragma unroll
     for (int e = 0; e < E; ++e) hs[j * E2 + hf * E + e] = fmaf(hj[hf * E + e], sc, sh);
   }
   __syncthreads();
-  if (j < A * E2) {
-    const int ai = j / E2, e = j - ai * E2;
-    const float* pk = pkof(e);
-    const float* w = pk + L.head_w + ai * kHid;
-    float s = 0.f;
-    for (int k = 0; k < kHid; ++k) s = fmaf(w[k], hs[k * E2 + e], s);
-    logit[e * kMaxAct + ai] = s + pk[L.head_b + ai];
-  }
+  head_rows<E, E2>(pk0, pk1, L, A, hs, logit);
   __syncthreads();
   if (j < E2) core_finish<E, kRollout>(a, logit + (j >= E ? E * kMaxAct : 0), l0 + (j >= E ? 1 : 0), j % E);
 }
@@ -763,6 +705,7 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel_pr(Layout L, StepArg
   const float* pk1 = pk0 + a.pack_stride;
   const float sg0 = a.sign ? (float)a.sign[l0] : 1.f, sg1 = a.sign ? (float)a.sign[l0 + 1] : 1.f;
   const float* ep = a.ep32 + (int64_t)pr * a.ep_stride;
+  const PairF32<E> P{pk0, pk1, ep, sg0, sg1};
   const int64_t e0 = (int64_t)l0 * E;
   const int A = a.n_act;
   float cj[E2];
@@ -784,41 +727,24 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel_pr(Layout L, StepArg
     for (int k = 0; k < kHid; ++k) {
       const float4 t = tl[(int64_t)(kCoreIn + k) * (kGates / 4)];
       const float4 d = ld_stream(dl + (int64_t)(kCoreIn + k) * (kGates / 4));
-      const float tp[4] = {fmaf(sg0, d.x, t.x), fmaf(sg0, d.y, t.y), fmaf(sg0, d.z, t.z), fmaf(sg0, d.w, t.w)};
-      const float tm[4] = {fmaf(sg1, d.x, t.x), fmaf(sg1, d.y, t.y), fmaf(sg1, d.z, t.z), fmaf(sg1, d.w, t.w)};
-#pragma unroll
-      for (int e = 0; e < E2; ++e) {
-        const float xv = hs[k * E2 + e];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ah[c][e] = fmaf(e < E ? tp[c] : tm[c], xv, ah[c][e]);
-      }
+      P.accum(ah, t, d, hs + k * E2);
     }
     const float4* g4 = reinterpret_cast<const float4*>(a.gx + ((int64_t)(a.t - a.gx_t0) * a.n_lanes * E + e0) * kGates);
-    const float4 bi0 = reinterpret_cast<const float4*>(pk0 + L.lstm_bih)[j];
-    const float4 bh0 = reinterpret_cast<const float4*>(pk0 + L.lstm_bhh)[j];
-    const float4 bi1 = reinterpret_cast<const float4*>(pk1 + L.lstm_bih)[j];
-    const float4 bh1 = reinterpret_cast<const float4*>(pk1 + L.lstm_bhh)[j];
-    const float bif0[4] = {bi0.x, bi0.y, bi0.z, bi0.w}, bhf0[4] = {bh0.x, bh0.y, bh0.z, bh0.w};
-    const float bif1[4] = {bi1.x, bi1.y, bi1.z, bi1.w}, bhf1[4] = {bh1.x, bh1.y, bh1.z, bh1.w};
+    const auto gb = P.gate_bias(L, j);
 #pragma unroll
     for (int e = 0; e < E2; ++e) {
       const float4 g = ld_stream(g4 + (int64_t)e * (kGates / 4) + j);
       const float gxv[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
-        xw[(4 * j + c) * E2 + e] = (gxv[c] + (e < E ? bif0[c] : bif1[c])) + (ah[c][e] + (e < E ? bhf0[c] : bhf1[c]));
+      for (int c = 0; c < 4; ++c) xw[(4 * j + c) * E2 + e] = P.gate_pre(gb, c, e, gxv[c], ah[c][e]);
     }
   }
   __syncthreads();
   float hj[E2];
 #pragma unroll
   for (int e = 0; e < E2; ++e) {
-    const float gi = sigm(xw[j * E2 + e]);
-    const float gf = sigm(xw[(kHid + j) * E2 + e]);
-    const float gg = tanhf(xw[(2 * kHid + j) * E2 + e]);
-    const float go = sigm(xw[(3 * kHid + j) * E2 + e]);
-    cj[e] = fmaf(gf, cj[e], gi * gg);  // explicit: the same rounding in every core form
-    hj[e] = go * tanhf(cj[e]);
+    FDR_LSTM_CELL(sigm, tanhf, xw[j * E2 + e], xw[(kHid + j) * E2 + e], xw[(2 * kHid + j) * E2 + e],
+                  xw[(3 * kHid + j) * E2 + e], cj[e], hj[e])
     a.h[(e0 + e) * kHid + j] = hj[e];
     a.c[(e0 + e) * kHid + j] = cj[e];
   }
@@ -826,23 +752,14 @@ __global__ __launch_bounds__(kCoreThreads) void core_kernel_pr(Layout L, StepArg
 #pragma unroll
   for (int hf = 0; hf < 2; ++hf) {
     const float* pk = hf ? pk1 : pk0;
-    const float rmv = (a.bn_mean ? a.bn_mean + L.bn_stat[16] : pk)[j];  // branch-free (see conv_kernel's table)
-    const float rvv = (a.bn_var ? a.bn_var + L.bn_stat[16] : pk)[j];
-    const float rm = a.bn_mean ? rmv : 0.f, rv = a.bn_var ? rvv : 1.f;
-    const float sc = pk[L.bn_w[16] + j] * (1.f / sqrtf(rv + kBnEps));
-    const float sh = fmaf(-rm, sc, pk[L.bn_b[16] + j]);
+    FDR_BN1D_STATS(16, j, pk, rm, rv)
+    float sc, sh;
+    FDR_BN1D_FOLD(pk[L.bn_w[16] + j], pk[L.bn_b[16] + j], rm, rv, sc, sh)
 #pragma unroll
     for (int e = 0; e < E; ++e) hs[j * E2 + hf * E + e] = fmaf(hj[hf * E + e], sc, sh);
   }
   __syncthreads();
-  if (j < A * E2) {
-    const int ai = j / E2, e = j - ai * E2;
-    const float* pk = e < E ? pk0 : pk1;
-    const float* w = pk + L.head_w + ai * kHid;
-    float s = 0.f;
-    for (int k = 0; k < kHid; ++k) s = fmaf(w[k], hs[k * E2 + e], s);
-    logit[e * kMaxAct + ai] = s + pk[L.head_b + ai];
-  }
+  head_rows<E, E2>(pk0, pk1, L, A, hs, logit);
   __syncthreads();
   if (j < E2) core_finish<E, kReplay>(a, logit + (j >= E ? E * kMaxAct : 0), l0 + (j >= E ? 1 : 0), j % E);
 }
@@ -954,11 +871,8 @@ __global__ __launch_bounds__(256) void fc_rows_kernel(Layout L, StepArgs a, int 
     for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = 0; k0 < kFeat; k0 += KC) {
     const int kk = k0 + (tid & 31);  // every X element this thread loads has this k
-    const float rmv = (a.bn_mean ? a.bn_mean + L.bn_stat[15] : a.pack)[kk];  // branch-free
-    const float rvv = (a.bn_var ? a.bn_var + L.bn_stat[15] : a.pack)[kk];
-    const float rm = a.bn_mean ? rmv : 0.f, rv = a.bn_var ? rvv : 1.f;
-    const float sc = pk[L.bn_w[15] + kk] * (1.f / sqrtf(rv + kBnEps));
-    const float sh = fmaf(-rm, sc, pk[L.bn_b[15] + kk]);
+    float sc, sh;
+    bn1d_fold(L, pk, 15, kk, bn1d_stats(L, a, 15, kk, a.pack), sc, sh);
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
       const int i = tid + 256 * m, row = i >> 5, q = row0 + row;

@@ -12,15 +12,13 @@
 #include <cfloat>
 #include <cmath>
 
-#include "fdr_impala_kernels.h"
+#include "fdr_impala_core.h"
 
 namespace fdr {
 namespace impala {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // pixel stride (halves) of an MFMA input image: unpadded (the chunk swizzle below spreads the banks); the
 // frame image keeps its 4 channel slots.
@@ -66,8 +64,6 @@ struct KSteps {
   static constexpr bool kRem = CIN == 3 || CIN == 16;
   static constexpr int NF = kRem ? N - 1 : N;  // full K = 32 steps
 };
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Cin = 16: the last fragment in the K = 16 layout (lane (o, g) holds tap 8 channels 4g .. 4g+3), read
 // straight from the K = 32 layout of the pack / WB (lane (o, g') holds k = 128 + 8g' .. +7, i.e. tap 8
@@ -1173,10 +1169,8 @@ __global__ __launch_bounds__(kCoreThreads) __attribute__((amdgpu_waves_per_eu(E 
 
   if constexpr (!seq_mode(MODE)) {
     for (int k = j; k < kFeat; k += kCoreThreads) {
-      const float rm = a.bn_mean ? a.bn_mean[L.bn_stat[15] + k] : 0.f;
-      const float rv = a.bn_var ? a.bn_var[L.bn_stat[15] + k] : 1.f;
-      const float sc = pk[L.bn_w[15] + k] * (1.f / sqrtf(rv + kBnEps));
-      const float sh = fmaf(-rm, sc, pk[L.bn_b[15] + k]);
+      float sc, sh;
+      bn1d_fold(L, pk, 15, k, bn1d_stats(L, a, 15, k, a.pack), sc, sh);
 #pragma unroll
       for (int e = 0; e < E; ++e) xw[k * E + e] = fmaf(a.feat[(e0 + e) * kFeat + k], sc, sh);
     }
@@ -1223,26 +1217,13 @@ __global__ __launch_bounds__(kCoreThreads) __attribute__((amdgpu_waves_per_eu(E 
     }
     if (MODE == kRollout && a.ci) {
       __syncthreads();
-      float* dst = a.ci + ((int64_t)a.t * a.n_lanes * E + e0) * kCoreIn;
-      for (int i = j; i < kCoreIn * E; i += kCoreThreads) {
-        const int e = i / kCoreIn, k = i - e * kCoreIn;
-        dst[i] = cis[k * E + e];
-      }
+      store_ci_rows<E>(ci_step<E>(a, e0), cis);
     }
   } else if (!a.gx) {
-    const float* src = a.ci + ((int64_t)a.t * a.n_lanes * E + e0) * kCoreIn;
-    for (int i = j; i < kCoreIn * E; i += kCoreThreads) {
-      const int e = i / kCoreIn, k = i - e * kCoreIn;
-      cis[k * E + e] = src[i];
-    }
+    load_ci_rows<E>(ci_step<E>(a, e0), cis);
   }
   float cj[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const float nd = (MODE == kForward && a.notdone) ? a.notdone[e0 + e] : 1.f;
-    hs[j * E + e] = nd * a.h[(e0 + e) * kHid + j];
-    cj[e] = nd * a.c[(e0 + e) * kHid + j];
-  }
+  load_state<E, MODE>(a, e0, j, hs, cj);
   __syncthreads();
   if (seq_mode(MODE) && a.gx) {
     // replay with x W_ih^T precomputed (lstm_xproj_kernel<true>): all 256 threads stream W_hh^T,
@@ -1314,40 +1295,29 @@ __global__ __launch_bounds__(kCoreThreads) __attribute__((amdgpu_waves_per_eu(E 
       const int col = g * kHid + j;
       pre[g] = (xw[col * E + e] + pk[L.lstm_bih + col]) + (xw[(kGates + col) * E + e] + pk[L.lstm_bhh + col]);
     }
-    const float gi = sigm(pre[0]), gf = sigm(pre[1]), gg = tanhf(pre[2]), go = sigm(pre[3]);
-    cj[e] = fmaf(gf, cj[e], gi * gg);  // explicit: the same rounding in every core form
-    hj[e] = go * tanhf(cj[e]);
+    hj[e] = lstm_cell<false>(pre, cj[e]);
     a.h[(e0 + e) * kHid + j] = hj[e];
     a.c[(e0 + e) * kHid + j] = cj[e];
   }
   {
-    const float rm = a.bn_mean ? a.bn_mean[L.bn_stat[16] + j] : 0.f;
-    const float rv = a.bn_var ? a.bn_var[L.bn_stat[16] + j] : 1.f;
-    const float sc = pk[L.bn_w[16] + j] * (1.f / sqrtf(rv + kBnEps));
-    const float sh = fmaf(-rm, sc, pk[L.bn_b[16] + j]);
+    float sc, sh;
+    bn1d_fold(L, pk, 16, j, bn1d_stats(L, a, 16, j, pk), sc, sh);
 #pragma unroll
     for (int e = 0; e < E; ++e) hs[j * E + e] = fmaf(hj[e], sc, sh);
   }
   __syncthreads();
-  if (j < A * E) {  // head in f32 (A x 256, tiny)
-    const int ai = j / E, e = j - ai * E;
-    const float* w = pk + L.head_w + ai * kHid;
-    float s = 0.f;
-    for (int k = 0; k < kHid; ++k) s = fmaf(w[k], hs[k * E + e], s);
-    logit[e * kMaxAct + ai] = s + pk[L.head_b + ai];
-  }
+  head_rows<E, E>(pk, pk, L, A, hs, logit);  // in f32 (A x 256, tiny)
   __syncthreads();
   if (j < E) core_finish<E, MODE>(a, logit, lane, j);
 }
 
-// ---- MFMA form of the fp16 pair core step (ctx core_mfma, the default) ---------------------------------------
-// The pair's lanes share theta and sigma-eps E, so each GEMM of the step is  W_l x = theta x + s_l (E x):
-// one v_mfma_f32_16x16x32_f16 of theta's A fragment against the B fragment X (the pair's 2E envs as columns,
-// repeated to 16) and one of E's fragment against S X (the columns of the minus lane sign-flipped), chained
-// into ONE f32 accumulator per 16-column tile.  The VALU form (core_kernel_hp) issues 96 VALU instructions per
-// 32 streamed bytes and leaves the HBM stream latency-bound at 2 waves/SIMD; here the VALU work is gone and
-// the weights stream through a 4-deep register ring (the images hold the A fragments in HBM order, 1 KB per
-// wave-load).  Activations x, the fc output and h are rounded to f16 as the B operand (fp16 tolerance).
+// ---- MFMA form of the fp16 pair core step ---------------------------------------------------------------------------
+// Each GEMM of the pair step is  W_l x = theta x + s_l (E x)  on v_mfma_f32_16x16x32_f16 over fragment images of
+// theta's and the pairs' sigma-eps half packs (the operand scheme, the masked-column argument, the weight ring
+// MfmaRing2 and the 3-MFMA tile body pair_mma3: fdr_impala_core.h).  Streaming the f16 weights through the VALU instead, as core_kernel_h does per lane,
+// costs 96 VALU instructions per 32 streamed bytes and left a pair kernel's HBM stream latency-bound at 2 waves/SIMD
+// (the experiment that introduced the MFMA form); here the VALU work is gone and the weights stream through a 4-deep
+// register ring.
 
 // MFMA images of n half packs: block (k-step, 256-column quarter) of W^T -> LDS -> fragments [ks][nt][l][8].
 __global__ __launch_bounds__(256) void mfma_image_kernel(Layout L, const _Float16* src, int64_t src_stride,
@@ -1378,93 +1348,21 @@ __global__ __launch_bounds__(256) void mfma_image_kernel(Layout L, const _Float1
   }
 }
 
-// ---- Two pairs per workgroup (ctx core_mfma = 2, the default) ------------------------------------------------------
-// theta's fragment of a k-step is the same for every pair, yet core_kernel_hpm loads it once per pair from L2 next to
-// the pair's streamed E (the probe build without those loads ran the launch 16 % faster: 0.237 -> 0.199 ms at config
-// 5).  Here a workgroup of 8 waves takes two pairs -- 4 lanes, their 4E envs as the B columns -- and issues per
-// 16-column tile and k-step  theta x X,  E_0 x (S X masked to pair 0's columns),  E_1 x (S X masked to pair 1's):
-// three MFMAs for two pairs where the one-pair form issues four, theta read once for both.  A masked column adds
-// exact zeros, so every accumulator sees core_kernel_hpm's products in its order: the two forms agree bit for bit.
-template <int NQ, class Frag>
-struct MfmaRing2 {
-  static constexpr int D = 4;
-  static_assert(NQ % D == 0, "ring depth divides the step count");
-  const _Float16* thm;
-  const _Float16* ep0;
-  const _Float16* ep1;
-  Frag frag;
-  h8 rt[D][2], ra[D][2], rb[D][2];
-  __device__ __forceinline__ void issue(int q, h8 (&t)[2], h8 (&ea)[2], h8 (&eb)[2]) {
-    const int64_t o = frag(q);
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt) {
-      t[jt] = *reinterpret_cast<const h8*>(thm + o + 512 * jt);
-      ea[jt] = ld_stream(reinterpret_cast<const h8*>(ep0 + o + 512 * jt));
-      eb[jt] = ld_stream(reinterpret_cast<const h8*>(ep1 + o + 512 * jt));
-    }
-  }
-  __device__ __forceinline__ void prime() {
-#pragma unroll
-    for (int u = 0; u < D - 1; ++u) issue(u, rt[u], ra[u], rb[u]);
-  }
-  template <class Mma>
-  __device__ __forceinline__ void run(Mma&& mma) {
-#pragma unroll 1
-    for (int q0 = 0; q0 < NQ; q0 += D) {
-#pragma unroll
-      for (int u = 0; u < D; ++u) {
-        const int q = q0 + u;
-        const int v = (u + D - 1) % D;
-        issue(min(q + D - 1, NQ - 1), rt[v], ra[v], rb[v]);  // past the end: a re-read
-        __builtin_amdgcn_sched_barrier(0);
-        mma(q, rt[u], ra[u], rb[u]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-};
-template <int NQ, class Frag>
-__device__ __forceinline__ MfmaRing2<NQ, Frag> mfma_ring2(const _Float16* thm, const _Float16* ep0, const _Float16* ep1,
-                                                          Frag f) {
-  return MfmaRing2<NQ, Frag>{thm, ep0, ep1, f};
-}
-
-// The head logits of a workgroup's NE envs (policies/impala.py:122): logit[e][ai] = b[ai] + sum_k W[ai][k] hs[k][e],
-// split over the 512 threads -- P parts of 256 / P inputs each, the parts added in part order (P = 8 at A * NE <= 64).
-// (One wave walking the 256 dependent FMAs per logit left the other seven waiting at the next barrier.)
-template <int E, int NE>
-__device__ __forceinline__ void head_split(const float* pack, int64_t pack_stride, int l0, const Layout& L, int A,
-                                           const float* hs, float* part, float* logit) {
-  const int j = threadIdx.x, nl = A * NE;
-  const int parts = nl <= 64 ? 8 : (nl <= 128 ? 4 : (nl <= 256 ? 2 : 1));
-  const int kn = kHid / parts;
-  if (j < parts * nl) {
-    const int pi = j / nl, r = j - pi * nl, ai = r / NE, e = r - ai * NE;
-    const float* wh = pack + (int64_t)(l0 + e / E) * pack_stride + L.head_w + ai * kHid + pi * kn;
-    const float* hp = hs + (pi * kn) * NE + e;
-    float s = 0.f;
-    for (int k = 0; k < kn; ++k) s = fmaf(wh[k], hp[k * NE], s);
-    part[j] = s;
-  }
-  __syncthreads();
-  if (j < nl) {
-    const int ai = j / NE, e = j - ai * NE;
-    float s = part[j];
-    for (int pi = 1; pi < parts; ++pi) s += part[pi * nl + j];
-    logit[e * kMaxAct + ai] = s + pack[(int64_t)(l0 + e / E) * pack_stride + L.head_b + ai];
-  }
-}
-
+// ---- The rollout step, two pairs per workgroup ---------------------------------------------------------------------
+// Operand scheme, ring, 3-MFMA tile body, cell, BN1d fold and head_split are fdr_impala_core.h's, as are the sign
+// masks with bfrag, the bias table with gh's pad and the gate GEMM (the FDR_PAIR2_* macros, shared with
+// replay_chunk_hpm2).  Wave w owns fc column tiles 2w, 2w + 1 and gate column tiles 8w .. 8w + 7; thread j owns hidden
+// unit u = j mod 256 of pair hf = j / 256's 2E envs in the cell / BN phases.  LDS: xh, the BN'd features as f16 B rows [env][XP], aliased by the f32 gate pre-activations gates
+// [col][NE] once the fc is done; gh, the gate GEMM's B rows [env][GP] = [x (256) | clip(r) | h (256) | zeros to
+// kGateKS * 32].  Both pitches carry 16 extra halves (32 B), which spread the 16 rows of a fragment read over the banks.
 template <int E, int MODE>
 __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_eu(2))) void core_kernel_hpm2(
     Layout L, StepArgs a) {
   constexpr int E2 = 2 * E, NE = 4 * E;  // envs of a pair / of the workgroup's 4 lanes
   // the rollout step only: the sequence modes run whole chunks per launch (replay_chunk_hpm2 below)
   static_assert(MODE == kRollout, "core_kernel_hpm2 is the rollout step");
-  constexpr bool kRep = false;
-  constexpr int kKs0 = kRep ? kCoreIn / 32 : 0, kNks = kGateKS - kKs0;
   static_assert(NE <= 16 && (NE & (NE - 1)) == 0, "the workgroup's envs are the B operand's columns (mod NE)");
-  constexpr int XP = kFeat + 16, GP = kGateKS * 32 + 16;  // f16 pitches, as core_kernel_hpm
+  constexpr int XP = kFeat + 16, GP = kGateKS * 32 + 16;  // f16 row pitches: + 32 B, see gh below
   constexpr int kXBytes = NE * XP * 2, kGBytes = kGates * NE * 4;
   __shared__ __attribute__((aligned(16))) char xg[kXBytes > kGBytes ? kXBytes : kGBytes];
   __shared__ __attribute__((aligned(16))) _Float16 gh[NE * GP];
@@ -1482,60 +1380,18 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
   const _Float16* ep1 = ep0 + kMImg;
   // wave w: fc column tiles 2w, 2w + 1; gate column tiles 8w .. 8w + 7, two at a time
   auto fc_ring = mfma_ring2<kFcKS>(a.thm, ep0, ep1, [w, l](int q) { return ((int64_t)(q * kFcNT + 2 * w) * 64 + l) * 8; });
-  auto gate_ring = mfma_ring2<4 * kNks>(a.thm + kFcImg, ep0 + kFcImg, ep1 + kFcImg, [w, l](int q) {
-    const int g = q / kNks, ks = kKs0 + q - g * kNks;
-    return ((int64_t)(ks * kGateNT + 8 * w + 2 * g) * 64 + l) * 8;
-  });
-  if constexpr (kRep)
-    gate_ring.prime();
-  else
-    fc_ring.prime();
+  auto gate_ring = gate_ring2<0>(a, ep0, ep1, w, l);
+  fc_ring.prime();
   const int64_t e0 = (int64_t)l0 * E;
   const int ep_ = hf * E2;  // this thread's first env in the workgroup (cell / BN roles)
-  float gxv[kRep ? E2 : 1][4];
-  if constexpr (kRep) {
-    const float* g = a.gx + ((int64_t)(a.t - a.gx_t0) * a.n_lanes * E + e0 + ep_) * kGates + u;
-#pragma unroll
-    for (int e = 0; e < E2; ++e)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) gxv[e][q] = g[(int64_t)e * kGates + q * kHid];
-  }
-  const int8_t* sgp = a.sign ? a.sign + l0 : reinterpret_cast<const int8_t*>(a.pack);  // branch-free
-  const int8_t sg0 = sgp[0], sg1 = sgp[1], sg2 = sgp[2], sg3 = sgp[3];
-  const int A = a.n_act;
-  // this lane's B column: env benv of the workgroup (lane bl, pair bl / 2); S X flips the minus lanes' columns and
-  // the two E operands see only their own pair's columns
-  const int benv = (l & 15) & (NE - 1), bl = benv / E;
-  const int8_t bsg = bl == 0 ? sg0 : (bl == 1 ? sg1 : (bl == 2 ? sg2 : sg3));
-  const unsigned smask = (a.sign && bsg < 0) ? 0x80008000u : 0u;
-  const unsigned zmask = (a.sign && bsg == 0) ? 0u : ~0u;  // a sign-0 (unperturbed) lane: E adds exact zeros
-  const unsigned ma = (bl < 2 ? ~0u : 0u) & zmask, mb = (bl < 2 ? 0u : ~0u) & zmask;
-  auto bfrag = [&](const _Float16* rowp, int k0, h8& x, h8& xa, h8& xb) {
-    x = *reinterpret_cast<const h8*>(rowp + k0 + 8 * (l >> 4));
-    const u32x4 sx = __builtin_bit_cast(u32x4, x) ^ u32x4{smask, smask, smask, smask};
-    xa = __builtin_bit_cast(h8, sx & u32x4{ma, ma, ma, ma});
-    xb = __builtin_bit_cast(h8, sx & u32x4{mb, mb, mb, mb});
-  };
-
+  FDR_PAIR2_OPERANDS;
   float cj[E2];
 #pragma unroll
   for (int e = 0; e < E2; ++e) {
     gh[(ep_ + e) * GP + kCoreIn + u] = (_Float16)a.h[(e0 + ep_ + e) * kHid + u];
     cj[e] = a.c[(e0 + ep_ + e) * kHid + u];
   }
-  for (int i = j; i < NE * (GP - kGateK); i += 2 * kCoreThreads) {
-    const int e = i / (GP - kGateK);
-    gh[e * GP + kGateK + i - e * (GP - kGateK)] = (_Float16)0.f;
-  }
-#pragma unroll
-  for (int it = 0; it < 4 * kGates / (2 * kCoreThreads); ++it) {
-    const int i = j + it * 2 * kCoreThreads, li = i / kGates, col = i & (kGates - 1);
-    const float* pk = pkl(li);
-    bsum[i] = pk[L.lstm_bih + col] + pk[L.lstm_bhh + col];
-  }
-  if constexpr (kRep) {
-    if (j < NE) gh[j * GP + kHid] = (_Float16)0.f;  // W_ih's reward row: its product is inside a.gx
-  } else {
+  FDR_PAIR2_TABLES
   float4 fcb[2];
 #pragma unroll
   for (int jt = 0; jt < 2; ++jt)
@@ -1592,12 +1448,7 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
     fc_ring.run([&](int q, const h8 (&tf)[2], const h8 (&fa)[2], const h8 (&fb)[2]) {
       h8 x, xa, xb;
       bfrag(xrow, 32 * q, x, xa, xb);
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(tf[jt], x, acc[jt], 0, 0, 0);
-        acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[jt], xa, acc[jt], 0, 0, 0);
-        acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[jt], xb, acc[jt], 0, 0, 0);
-      }
+      pair_mma3(acc, tf, fa, fb, x, xa, xb);
     });
     gate_ring.prime();
     if ((l & 15) < NE) {
@@ -1613,7 +1464,6 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
         }
     }
   }
-  }  // !kRep
   __syncthreads();
   if (a.ci16) {  // the gate rows' x part as f16 core inputs for the replay's x W_ih^T (zero beyond kCoreIn)
     constexpr int kR8 = kCiPitch / 8;
@@ -1626,31 +1476,7 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
       *reinterpret_cast<h8*>(dst + e * kCiPitch + k8) = v;
     }
   }
-  {  // gates
-    f32x4 acc[2];
-    const _Float16* grow = gh + benv * GP;
-    gate_ring.run([&](int q, const h8 (&tf)[2], const h8 (&fa)[2], const h8 (&fb)[2]) {
-      const int g = q / kNks, ks = kKs0 + q - g * kNks;
-      if (ks == kKs0)
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt) acc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      h8 x, xa, xb;
-      bfrag(grow, 32 * ks, x, xa, xb);
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(tf[jt], x, acc[jt], 0, 0, 0);
-        acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[jt], xa, acc[jt], 0, 0, 0);
-        acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[jt], xb, acc[jt], 0, 0, 0);
-      }
-      if (ks == kGateKS - 1 && (l & 15) < NE) {
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            gates[(16 * (8 * w + 2 * g + jt) + 4 * (l >> 4) + i) * NE + (l & 15)] = acc[jt][i];
-      }
-    });
-  }
+  FDR_PAIR2_GATE_GEMM(gate_ring, 0, gates)
   __syncthreads();
   float hj[E2];
 #pragma unroll
@@ -1661,24 +1487,17 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
     for (int g = 0; g < 4; ++g) {
       const int col = g * kHid + u;
       pre[g] = gates[col * NE + we] + bsum[(we / E) * kGates + col];
-      if constexpr (kRep) pre[g] += gxv[e][g];
     }
-    auto sg = [](float x) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x)); };
-    const float gi = sg(pre[0]), gf = sg(pre[1]), gg = tanh_fast(pre[2]), go = sg(pre[3]);
-    cj[e] = fmaf(gf, cj[e], gi * gg);  // explicit: the same rounding in every core form
-    hj[e] = go * tanh_fast(cj[e]);
+    hj[e] = lstm_cell<true>(pre, cj[e]);
     a.h[(e0 + we) * kHid + u] = hj[e];
     a.c[(e0 + we) * kHid + u] = cj[e];
   }
   {
-    const float rmv = (a.bn_mean ? a.bn_mean + L.bn_stat[16] : a.pack)[u];  // branch-free
-    const float rvv = (a.bn_var ? a.bn_var + L.bn_stat[16] : a.pack)[u];
-    const float rm = a.bn_mean ? rmv : 0.f, rv = a.bn_var ? rvv : 1.f;
+    const Bn1dStats st = bn1d_stats(L, a, 16, u, a.pack);
 #pragma unroll
     for (int h2i = 0; h2i < 2; ++h2i) {  // the pair's two lanes
-      const float* pk = pkl(2 * hf + h2i);
-      const float sc = pk[L.bn_w[16] + u] * (1.f / sqrtf(rv + kBnEps));
-      const float sh = fmaf(-rm, sc, pk[L.bn_b[16] + u]);
+      float sc, sh;
+      bn1d_fold(L, pkl(2 * hf + h2i), 16, u, st, sc, sh);
 #pragma unroll
       for (int e = 0; e < E; ++e) hs[u * NE + ep_ + h2i * E + e] = fmaf(hj[h2i * E + e], sc, sh);
     }
@@ -1692,19 +1511,22 @@ template __global__ void core_kernel_hpm2<1, kRollout>(Layout, StepArgs);
 template __global__ void core_kernel_hpm2<2, kRollout>(Layout, StepArgs);
 template __global__ void core_kernel_hpm2<4, kRollout>(Layout, StepArgs);
 
-// ---- The entropy replay of a whole chunk per launch (ctx core_mfma = 2) -----------------------------------------------
-// A per-step replay launch (two pairs per workgroup) streamed the pairs' W_hh images in ~38 us of its ~62 at config 5
-// and spent the rest on its prologue (h / c / biases / signs) and epilogue (cell, BN1d, head, entropy).  The pairs'
-// sequences are independent, so one workgroup runs every step of the chunk for its two pairs: the prologue runs once,
-// h / c / the entropy sums stay in registers, and the next step's first fragments load under the epilogue (the
-// weights do not depend on h).  Each step is core_kernel_hpm<E, kReplay>'s arithmetic in its order: bitwise equal to
-// the one-pair form (core_mfma 1) over whole episodes.
+// ---- The entropy replay of a whole chunk per launch ----------------------------------------------------------------
+// One replay step streams the pairs' W_hh images in ~38 us; launched per step it took ~62 us at config 5, the rest
+// its prologue (h / c / biases / signs) and epilogue (cell, BN1d, head, entropy) -- figures of the experiment that
+// introduced this kernel.  The pairs' sequences are independent, so one workgroup runs every step of the chunk for its
+// two pairs: the prologue runs once, h / c / the entropy sums stay in registers, and the next step's first fragments
+// load under the epilogue (the weights do not depend on h).  A step is the rollout step's gate phase onward over
+// k-steps kCoreIn / 32 .. kGateKS - 1 (W_hh^T; the reward row of that first k-step is zeroed in gh, its product is
+// inside a.gx) plus a.gx's x W_ih^T.  Chunking changes no value: between steps h passes through the same f16 rounding
+// into gh that a reload of the stored f32 h would apply, c stays f32 and the entropy sum continues from a.ent in step
+// order -- the chunk is bitwise equal to launching this kernel once per step (tc = 1), wherever the chunks are cut.
 template <int E, int MODE>
 __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_eu(2))) void replay_chunk_hpm2(
     Layout L, StepArgs a, int t0, int tc) {
   static_assert(MODE == kReplay || MODE == kStrategy, "sequence modes");
   constexpr int E2 = 2 * E, NE = 4 * E;
-  constexpr int kKs0 = kCoreIn / 32, kNks = kGateKS - kKs0, NQ = 4 * kNks;
+  constexpr int kKs0 = kCoreIn / 32;  // the gate images' first W_hh^T k-step
   static_assert(NE <= 16 && (NE & (NE - 1)) == 0, "the workgroup's envs are the B operand's columns (mod NE)");
   constexpr int GP = kGateKS * 32 + 16;
   __shared__ __attribute__((aligned(16))) float gates[kGates * NE];
@@ -1719,27 +1541,11 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
   auto pkl = [&](int li) { return a.pack + (int64_t)(l0 + li) * a.pack_stride; };
   const _Float16* ep0 = a.epm + (int64_t)(2 * blockIdx.x) * kMImg;
   const _Float16* ep1 = ep0 + kMImg;
-  auto ring = mfma_ring2<NQ>(a.thm + kFcImg, ep0 + kFcImg, ep1 + kFcImg, [w, l](int q) {
-    const int g = q / kNks, ks = kKs0 + q - g * kNks;
-    return ((int64_t)(ks * kGateNT + 8 * w + 2 * g) * 64 + l) * 8;
-  });
+  auto ring = gate_ring2<kKs0>(a, ep0, ep1, w, l);
   ring.prime();
   const int64_t e0 = (int64_t)l0 * E;
   const int ep_ = hf * E2;
-  const int8_t* sgp = a.sign ? a.sign + l0 : reinterpret_cast<const int8_t*>(a.pack);  // branch-free
-  const int8_t sg0 = sgp[0], sg1 = sgp[1], sg2 = sgp[2], sg3 = sgp[3];
-  const int A = a.n_act;
-  const int benv = (l & 15) & (NE - 1), bl = benv / E;
-  const int8_t bsg = bl == 0 ? sg0 : (bl == 1 ? sg1 : (bl == 2 ? sg2 : sg3));
-  const unsigned smask = (a.sign && bsg < 0) ? 0x80008000u : 0u;
-  const unsigned zmask = (a.sign && bsg == 0) ? 0u : ~0u;
-  const unsigned ma = (bl < 2 ? ~0u : 0u) & zmask, mb = (bl < 2 ? 0u : ~0u) & zmask;
-  auto bfrag = [&](const _Float16* rowp, int k0, h8& x, h8& xa, h8& xb) {
-    x = *reinterpret_cast<const h8*>(rowp + k0 + 8 * (l >> 4));
-    const u32x4 sx = __builtin_bit_cast(u32x4, x) ^ u32x4{smask, smask, smask, smask};
-    xa = __builtin_bit_cast(h8, sx & u32x4{ma, ma, ma, ma});
-    xb = __builtin_bit_cast(h8, sx & u32x4{mb, mb, mb, mb});
-  };
+  FDR_PAIR2_OPERANDS;
   float cj[E2], hj[E2];
 #pragma unroll
   for (int e = 0; e < E2; ++e) {
@@ -1747,29 +1553,14 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
     cj[e] = a.c[(e0 + ep_ + e) * kHid + u];
     hj[e] = 0.f;
   }
-  for (int i = j; i < NE * (GP - kGateK); i += 2 * kCoreThreads) {
-    const int e = i / (GP - kGateK);
-    gh[e * GP + kGateK + i - e * (GP - kGateK)] = (_Float16)0.f;
-  }
-#pragma unroll
-  for (int it = 0; it < 4 * kGates / (2 * kCoreThreads); ++it) {
-    const int i = j + it * 2 * kCoreThreads, li = i / kGates, col = i & (kGates - 1);
-    const float* pk = pkl(li);
-    bsum[i] = pk[L.lstm_bih + col] + pk[L.lstm_bhh + col];
-  }
+  FDR_PAIR2_TABLES
   if (j < NE) gh[j * GP + kHid] = (_Float16)0.f;  // W_ih's reward row: its product is inside a.gx
   // head BN1d of unit u for the pair's two lanes (constant over the chunk)
   float bsc[2], bsh[2];
   {
-    const float rmv = (a.bn_mean ? a.bn_mean + L.bn_stat[16] : a.pack)[u];  // branch-free
-    const float rvv = (a.bn_var ? a.bn_var + L.bn_stat[16] : a.pack)[u];
-    const float rm = a.bn_mean ? rmv : 0.f, rv = a.bn_var ? rvv : 1.f;
+    const Bn1dStats st = bn1d_stats(L, a, 16, u, a.pack);
 #pragma unroll
-    for (int h2i = 0; h2i < 2; ++h2i) {
-      const float* pk = pkl(2 * hf + h2i);
-      bsc[h2i] = pk[L.bn_w[16] + u] * (1.f / sqrtf(rv + kBnEps));
-      bsh[h2i] = fmaf(-rm, bsc[h2i], pk[L.bn_b[16] + u]);
-    }
+    for (int h2i = 0; h2i < 2; ++h2i) bn1d_fold(L, pkl(2 * hf + h2i), 16, u, st, bsc[h2i], bsh[h2i]);
   }
   // thread j < NE: env j's entropy sum, continued from a.ent in the per-step kernel's order and stored at the end
   double ent = MODE == kReplay ? a.ent[e0 + (j & (NE - 1))] : 0.0;
@@ -1784,31 +1575,7 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
         for (int q = 0; q < 4; ++q) gxv[e][q] = g[(int64_t)e * kGates + q * kHid];
     }
     __syncthreads();  // gh holds h_(t-1) (the prologue or the previous step's cell phase)
-    {
-      f32x4 acc[2];
-      const _Float16* grow = gh + benv * GP;
-      ring.run([&](int q, const h8 (&tf)[2], const h8 (&fa)[2], const h8 (&fb)[2]) {
-        const int g = q / kNks, ks = kKs0 + q - g * kNks;
-        if (ks == kKs0)
-#pragma unroll
-          for (int jt = 0; jt < 2; ++jt) acc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        h8 x, xa, xb;
-        bfrag(grow, 32 * ks, x, xa, xb);
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt) {
-          acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(tf[jt], x, acc[jt], 0, 0, 0);
-          acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[jt], xa, acc[jt], 0, 0, 0);
-          acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[jt], xb, acc[jt], 0, 0, 0);
-        }
-        if (ks == kGateKS - 1 && (l & 15) < NE) {
-#pragma unroll
-          for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              gates[(16 * (8 * w + 2 * g + jt) + 4 * (l >> 4) + i) * NE + (l & 15)] = acc[jt][i];
-        }
-      });
-    }
+    FDR_PAIR2_GATE_GEMM(ring, kKs0, gates)
     if (s + 1 < tc) ring.prime();  // the next step's first fragments, under this step's epilogue
     __syncthreads();
 #pragma unroll
@@ -1821,10 +1588,7 @@ __global__ __launch_bounds__(2 * kCoreThreads) __attribute__((amdgpu_waves_per_e
         pre[g] = gates[col * NE + we] + bsum[(we / E) * kGates + col];
         pre[g] += gxv[e][g];
       }
-      auto sg = [](float x) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x)); };
-      const float gi = sg(pre[0]), gf = sg(pre[1]), gg = tanh_fast(pre[2]), go = sg(pre[3]);
-      cj[e] = fmaf(gf, cj[e], gi * gg);  // explicit: the same rounding in every core form
-      hj[e] = go * tanh_fast(cj[e]);
+      hj[e] = lstm_cell<true>(pre, cj[e]);
       gh[we * GP + kCoreIn + u] = (_Float16)hj[e];  // the next step's B rows (read after its first barrier)
     }
 #pragma unroll

@@ -25,7 +25,7 @@ constexpr int kCiPitch = (kCoreIn + 31) / 32 * 32;
   } while (0)
 #endif
 
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
+// The core kernels' shared phases (cell, BN1d fold, head, pair operands, MFMA ring): fdr_impala_core.h, device-only.
 
 // ---- f32 kernels (fdr_impala_f32.hip) ----
 constexpr int kConvThreads = 512;

@@ -120,77 +120,68 @@ __device__ __forceinline__ void core_finish(const StepArgs& a, const float* logi
   const int at_t = t_step >= 0 ? t_step : a.t;
   const int A = a.n_act;
   const int64_t e0 = (int64_t)lane * E;
-    const int e = j;
-    const float* lg = logit + e * kMaxAct;
-    float mx = -FLT_MAX;
-    for (int i = 0; i < A; ++i) mx = fmaxf(mx, lg[i]);
-    float p[kMaxAct];
-    float sum = 0.f;
-    for (int i = 0; i < A; ++i) {
-      p[i] = expf(lg[i] - mx);
-      sum += p[i];
-    }
-    const float inv = 1.f / sum;
-    for (int i = 0; i < A; ++i) p[i] *= inv;
-    const int64_t ge = e0 + e;
-    if constexpr (MODE == kForward) {
-      if (a.probs)
-        for (int i = 0; i < A; ++i) a.probs[ge * A + i] = p[i];
-    } else if constexpr (MODE == kStrategy) {
-      for (int i = 0; i < A; ++i) a.probs[(ge * a.T + at_t) * A + i] = p[i];
-    } else if constexpr (MODE == kReplay) {
-      // torch Categorical(probs).entropy(): normalise, log clamped at float min
+  const int e = j;
+  const float* lg = logit + e * kMaxAct;
+  float mx = -FLT_MAX;
+  for (int i = 0; i < A; ++i) mx = fmaxf(mx, lg[i]);
+  float p[kMaxAct];
+  float sum = 0.f;
+  for (int i = 0; i < A; ++i) {
+    p[i] = expf(lg[i] - mx);
+    sum += p[i];
+  }
+  const float inv = 1.f / sum;
+  for (int i = 0; i < A; ++i) p[i] *= inv;
+  const int64_t ge = e0 + e;
+  if constexpr (MODE == kForward) {
+    if (a.probs)
+      for (int i = 0; i < A; ++i) a.probs[ge * A + i] = p[i];
+  } else if constexpr (MODE == kStrategy) {
+    for (int i = 0; i < A; ++i) a.probs[(ge * a.T + at_t) * A + i] = p[i];
+  } else if constexpr (MODE == kRollout) {
+    if (a.probs)
+      for (int i = 0; i < A; ++i) a.probs[(ge * a.T + a.t) * A + i] = p[i];
+    const uint64_t gid = (uint64_t)(a.lane_offset * E + ge);
+    int act = 0;
+    const bool det = a.deterministic && a.deterministic[lane];
+    if (det) {
+      float best = p[0];
+      for (int i = 1; i < A; ++i)
+        if (p[i] > best) { best = p[i]; act = i; }
+    } else {  // inverse CDF, sequential f32 cumsum (oracle/policies.py categorical_inverse_cdf)
       float tot = 0.f;
       for (int i = 0; i < A; ++i) tot += p[i];
-      float h = 0.f;
-      for (int i = 0; i < A; ++i) {
-        const float pn = p[i] / tot;
-        const float l = pn > 0.f ? logf(pn) : -FLT_MAX;
-        h -= pn * l;
-      }
-      if (ent_acc)
-        *ent_acc += (double)h;
-      else
-        a.ent[ge] += (double)h;
-    } else {
-      if (a.probs)
-        for (int i = 0; i < A; ++i) a.probs[(ge * a.T + a.t) * A + i] = p[i];
-      const uint64_t gid = (uint64_t)(a.lane_offset * E + ge);
-      int act = 0;
-      const bool det = a.deterministic && a.deterministic[lane];
-      if (det) {
-        float best = p[0];
-        for (int i = 1; i < A; ++i)
-          if (p[i] > best) { best = p[i]; act = i; }
-      } else {  // inverse CDF, sequential f32 cumsum (oracle/policies.py categorical_inverse_cdf)
-        float tot = 0.f;
-        for (int i = 0; i < A; ++i) tot += p[i];
-        const float u = uniform24(hash_ctr(a.akey, gid, (uint64_t)a.t, 0));
-        const float target = u * tot;
-        float cs = 0.f;
-        for (int i = 0; i < A - 1; ++i) {
-          cs += p[i];
-          act += cs <= target ? 1 : 0;
-        }
-      }
-      const uint64_t ctr = (gid << 32) | ((uint64_t)a.t << 11);
-      const int tgt = (int)((mix64(a.rkey + ctr * kGolden) >> 40) % (uint64_t)A);
-      const float r = act == tgt ? 1.f : (act == (tgt + 1) % A ? -1.f : 0.f);
-      a.ret[ge] += (double)r;
-      if (a.rprev) a.rprev[ge] = r;
-      if (a.actions) a.actions[ge * a.T + a.t] = act;
-      if (step_entropy) {  // stateless policies: the mean per-step entropy equals the batched one
-        float tot = 0.f;
-        for (int i = 0; i < A; ++i) tot += p[i];
-        float hh = 0.f;
-        for (int i = 0; i < A; ++i) {
-          const float pn = p[i] / tot;
-          const float l = pn > 0.f ? logf(pn) : -FLT_MAX;
-          hh -= pn * l;
-        }
-        a.ent[ge] += (double)hh;
+      const float u = uniform24(hash_ctr(a.akey, gid, (uint64_t)a.t, 0));
+      const float target = u * tot;
+      float cs = 0.f;
+      for (int i = 0; i < A - 1; ++i) {
+        cs += p[i];
+        act += cs <= target ? 1 : 0;
       }
     }
+    const uint64_t ctr = (gid << 32) | ((uint64_t)a.t << 11);
+    const int tgt = (int)((mix64(a.rkey + ctr * kGolden) >> 40) % (uint64_t)A);
+    const float r = act == tgt ? 1.f : (act == (tgt + 1) % A ? -1.f : 0.f);
+    a.ret[ge] += (double)r;
+    if (a.rprev) a.rprev[ge] = r;
+    if (a.actions) a.actions[ge * a.T + a.t] = act;
+  }
+  // The step's entropy term -- the replay's, or a stateless policy's rollout (step_entropy: its mean per-step entropy
+  // equals the batched one) -- as torch Categorical(probs).entropy(): normalise, log clamped at float min.
+  if (MODE == kReplay || (MODE == kRollout && step_entropy)) {
+    float tot = 0.f;
+    for (int i = 0; i < A; ++i) tot += p[i];
+    float h = 0.f;
+    for (int i = 0; i < A; ++i) {
+      const float pn = p[i] / tot;
+      const float l = pn > 0.f ? logf(pn) : -FLT_MAX;
+      h -= pn * l;
+    }
+    if (MODE == kReplay && ent_acc)
+      *ent_acc += (double)h;
+    else
+      a.ent[ge] += (double)h;
+  }
 }
 
 // Workspace carve-up of a call: consecutive 256-byte aligned regions, take() returns a region's byte offset

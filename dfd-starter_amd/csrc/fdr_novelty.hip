@@ -11,6 +11,8 @@ namespace fdr {
 // Strategy distances / novelty (utils/math_helpers.py:147-222, strategy/*): one 256-thread block
 // per strategy i holds it in LDS; each wave walks archive entries h = w, w+4, ..., its lanes over
 // the probe states z, f64 accumulation, fixed reduction order.  d[i][h] = mean_z term(a_iz, b_hz).
+// min / argmin follow numpy's (compute_strategy_novelty is np.min): the first minimum; a NaN distance wins and the
+// lowest NaN index is the argmin, so a strategy that holds a NaN scores NaN, never +inf (the most novel lane).
 // ------------------------------------------------------------------------------------------
 constexpr int kNovThreads = 256;
 constexpr int kNovMaxZD = 8192;  // floats of one strategy held in LDS (32 KiB)
@@ -51,15 +53,20 @@ __global__ __launch_bounds__(kNovThreads) void strategy_dist_kernel(const float*
     }
     acc = wave_sum(acc) / (double)Z;
     if (dists && lane == 0) dists[(int64_t)i * H + h] = acc;
-    if (acc < best) { best = acc; best_h = h; }  // h increases: first minimum kept
+    // h increases: the first minimum, or the first NaN, is kept
+    if (best_h < 0 || acc < best || (acc != acc && best == best)) { best = acc; best_h = h; }
   }
   if (lane == 0) { wmin[wave] = best; warg[wave] = best_h; }
   __syncthreads();
   if (threadIdx.x == 0) {
     double m = __builtin_inf();
     int am = -1;
-    for (int w = 0; w < kNovThreads / kWave; ++w)
-      if (warg[w] >= 0 && (wmin[w] < m || (wmin[w] == m && warg[w] < am))) { m = wmin[w]; am = warg[w]; }
+    for (int w = 0; w < kNovThreads / kWave; ++w) {
+      if (warg[w] < 0) continue;  // H < 4: the wave had no entry
+      const bool wnan = wmin[w] != wmin[w], mnan = m != m;
+      const bool take = wnan ? (!mnan || warg[w] < am) : (!mnan && (wmin[w] < m || (wmin[w] == m && warg[w] < am)));
+      if (am < 0 || take) { m = wmin[w]; am = warg[w]; }
+    }
     if (min_d) min_d[i] = m;
     if (arg) arg[i] = am;
   }

@@ -481,7 +481,8 @@ int fdr_fd_step_mix_opt(fdr_ctx* ctx, const float* table, int64_t table_size, co
  *   FDR_DIST_W2   ||m_a - m_b||^2 + sum(s_a + s_b - 2 sqrt(s_a s_b)), D = 2k = [mean | std]
  *                 (gaussian_wasserstein_dist_from_strategies :202-213)
  * f64 accumulation.  Outputs (each nullable): dists [n, H] f64; min_dist [n] f64 = the novelty of
- * compute_strategy_novelty (:147-155); argmin [n] i32 (first minimum).  Z * D <= 8192. */
+ * compute_strategy_novelty (:147-155); argmin [n] i32 (first minimum).  As np.min / np.argmin, a NaN distance wins:
+ * min_dist is then NaN and argmin the lowest index with a NaN distance.  Z * D <= 8192. */
 #define FDR_DIST_L2 0
 #define FDR_DIST_TVD 1
 #define FDR_DIST_W2 2

@@ -19,6 +19,10 @@ namespace fdr {
 //              3-level reduce-scatter of the one-lane kernel over 16 slots (8 + 4 + 2 DPP adds).
 //   head       thread (rho = t/16, o = t%16) sums W3[o][.] over the 32 units its own DPP row
 //              holds (32 row_newbcast FMAs), then the two rows of the half (one permlane16 swap).
+//   head, 12 outputs (kHeadRS: continuous, 6 actions): every thread multiplies its own two units into all 12
+//              outputs (12 packed FMAs against 24 W3 values), a 4-level reduce-scatter over the row (12 DPP
+//              adds and a select, tools/gen_dpp.py) leaves output 3 (o/4) + min(o%4, 2) in thread o -- means in threads
+//              0,1,2,4,5,6, std pre-activations 8 lanes up -- then the two rows as above.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPairWaves = 2;  // waves per workgroup (4 lanes): 4 workgroups, 8 waves per CU
 
@@ -50,7 +54,9 @@ struct MlpPair {
   static constexpr bool kPre = !DISC;  // tanh layers' weights stored x kTanhScale
   static constexpr float kWS = kPre ? kTanhScale : 1.f;
   static constexpr int kW1Chunks = kW1Lds ? NX / 4 : 0;     // per W1 row
-  static constexpr int kTileF4 = (2 * kW1Chunks + 8) * kWave;  // float4 per wave: W1 rows, W3 slice
+  static constexpr bool kHeadRS = !DISC && NOUT == 12;        // the reduce-scatter head (fdr_dpp_gen.h)
+  static constexpr int kW3Chunks = kHeadRS ? 6 : 8;           // float4 of W3 per thread
+  static constexpr int kTileF4 = (2 * kW1Chunks + kW3Chunks) * kWave;  // float4 per wave: W1 rows, W3 slice
   f2 w1a[kW1Lds ? 1 : NX / 2], w1b[kW1Lds ? 1 : NX / 2];
   float b1a, b1b;
   const float4* tile;  // this thread's column of the wave tile (chunk m at tile[m * kWave])
@@ -123,8 +129,19 @@ struct MlpPair {
     const int u2a = 8 * q4 + c4, u2b = 8 * q4 + 4 + c4;  // this thread's layer-2 units
     b2a = kWS * src.get(L::L2B + u2a);
     b2b = kWS * src.get(L::L2B + u2b);
-    // branch-free (MlpLane::load): clamped indices, counted and kept only where the element exists
-    {
+    if constexpr (kHeadRS) {
+      // register r of this thread holds output head_rs12_slot(o, r): W3 of the thread's two layer-2 units against all
+      // 12 outputs, every element read and counted once per lane.  Chunks 0-2: unit u2a (h2.x), 3-5: unit u2b (h2.y)
+#pragma unroll
+      for (int m = 0; m < 6; ++m) {
+        float e[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          e[i] = src.get(L::L3W + (int64_t)head_rs12_slot(o, 4 * (m % 3) + i) * kHidden + (m < 3 ? u2a : u2b));
+        my[(2 * kW1Chunks + m) * kWave] = float4{kWS * e[0], kWS * e[1], kWS * e[2], kWS * e[3]};
+      }
+      b3 = kWS * src.get_if(L::L3B + head_rs12_out(o), rho == 0 && c4 != 3);  // thread 4q + 3 repeats 4q + 2
+    } else {
       const bool has_o = o < NOUT;
       const int oc = has_o ? o : 0;
 #pragma unroll
@@ -343,7 +360,8 @@ struct MlpPair {
   }
 
   // Layer 2 and the head: h1 = this thread's layer-1 units (2t, 2t+1); h1s = the half's scratch.
-  // Returns the head pre-activation for output o = t & 15 (identical in both rows of the half).
+  // Returns the head pre-activation for output o = t & 15 (identical in both rows of the half); kHeadRS: for output
+  // head_rs12_out(t & 15).
   // Wave priority: low for the 64 independent layer-2 FMAs (from the h1 write on), raised for the serial part of the
   // step -- reduce-scatter, tanh, head, action, env, x hand-off, layer 1 -- so the SIMD's other wave yields to it
   template <class Mark>
@@ -354,9 +372,9 @@ struct MlpPair {
     __builtin_amdgcn_s_setprio(0);
     wave_lds_sync();
     lds_bcast<16>(h1s + 16 * c4, x);
-    float w3[32];
+    float w3[4 * kW3Chunks];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
+    for (int m = 0; m < kW3Chunks; ++m) {
       const float4 w = tile[(2 * kW1Chunks + m) * kWave];
       w3[4 * m] = w.x;
       w3[4 * m + 1] = w.y;
@@ -487,10 +505,18 @@ struct MlpPair {
       h2a = h2.x;
       h2b = h2.y;
     }
-    float u;
-    dpp_dot_32x1(u, h2a, h2b, w3);  // one chain of 32 (the accumulator is no DPP source: no wait states)
-    float v = u;
-    permlane16_swap(u, v);  // u = row 2h's partial, v = row 2h+1's, in both rows of half h
+    float u, v;  // u = row 2h's partial, v = row 2h+1's, in both rows of half h
+    if constexpr (kHeadRS) {
+      f2 w3p[12];
+#pragma unroll
+      for (int j = 0; j < 12; ++j) w3p[j] = f2{w3[2 * j], w3[2 * j + 1]};
+      // 12 packed products, 12 DPP adds, a select, the last add again and the row swap: one asm statement
+      dpp_head_rs12(u, v, w3p, f2{h2a, h2b});
+    } else {
+      dpp_dot_32x1(u, h2a, h2b, w3);  // one chain of 32 (the accumulator is no DPP source: no wait states)
+      v = u;
+      permlane16_swap(u, v);
+    }
     const float out = (u + v) + b3;
     mark(2, out);
     return out;

@@ -85,7 +85,13 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
   int n0 = T, n1 = T;                 // their env.step counts
   auto alive_me = [&]() { return hh ? alive1 : alive0; };
   float rbuf = 0.f;
-  const int zbase = 4 * (32 * hh + (DISC ? 0 : (o < NA ? o : 0)));
+  // continuous: action dim d's mean sits in row thread d -- or, behind the reduce-scatter head (Lane::kHeadRS), in row
+  // thread d + d / 3 (0, 1, 2, 4, 5, 6), its std pre-activation kStdShl threads above
+  constexpr bool kRS = Lane::kHeadRS;
+  constexpr int kStdShl = kRS ? 8 : NA;
+  int zbase;
+  if constexpr (kRS) zbase = 4 * (32 * hh + ((o < 8 && (o & 3) != 3) ? o - (o >> 2) : 0));
+  else zbase = 4 * (32 * hh + (DISC ? 0 : (o < NA ? o : 0)));
   auto* sc = &scratch[wv];
   [[maybe_unused]] float* xs = sc->x[hh];
   float* h1s = sc->h1[hh];
@@ -187,14 +193,16 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
       pre += mrow[NX + act_d];
     } else {
       const float th = tanh_act<Lane::kPre>(y);
-      const float sd = std_from_tanh(dpp_mov<kDppRowShl + NA>(th));
+      const float sd = std_from_tanh(dpp_mov<kDppRowShl + kStdShl>(th));
       if constexpr (kTerm)
         eacc += alive_me() ? __builtin_amdgcn_logf(sd) : 0.f;
       else
         eacc += __builtin_amdgcn_logf(sd);
       const float act_c = det ? th : gauss_action(th, sd, zt);
       mark(3, act_c);
-      dpp_tail<NA>(pre, act_c, kr);  // a[m] sits in thread m of both rows of the half
+      // a[m] sits in thread m (kRS: m + m / 3) of both rows of the half
+      if constexpr (kRS) dpp_tail_q3<NA>(pre, act_c, kr);
+      else dpp_tail<NA>(pre, act_c, kr);
     }
     s = tanh_pre(pre);  // M, K stored x kPreScale
     mark(4, s);
@@ -265,7 +273,9 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
     for (int k = 0; k < 5; ++k) g_phase_stamps[k] = ph_acc[k];
 #endif
   eacc *= 0.693147180559945309f;  // log2 -> ln (both kinds)
-  double esum = (t < NA) ? (double)eacc : 0.0;  // row 0 of the half: one copy of each output
+  double esum;  // row 0 of the half: one copy of each output
+  if constexpr (kRS) esum = (t < 8 && (t & 3) != 3) ? (double)eacc : 0.0;
+  else esum = (t < NA) ? (double)eacc : 0.0;
 #pragma unroll
   for (int m = 16; m >= 1; m >>= 1) esum += __shfl_xor(esum, m, kWave);
   if (t == 0 && active) {

@@ -19,9 +19,18 @@ __host__ __device__ __forceinline__ uint64_t mix64_a(uint64_t z) { return (z ^ (
 __host__ __device__ __forceinline__ uint64_t mix64_b(uint64_t z) { return (z ^ (z >> 27)) * 0x94D049BB133111EBull; }
 __host__ __device__ __forceinline__ uint64_t mix64_c(uint64_t z) { return z ^ (z >> 31); }
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) { return mix64_c(mix64_b(mix64_a(z))); }
+constexpr uint64_t kCtrMul = 0x9E3779B97F4A7C15ull;
 __device__ __forceinline__ uint64_t hash_ctr_word(uint64_t key, uint64_t lane, uint64_t t, uint64_t k) {
   const uint64_t c = (lane << 32) | (t << 4) | k;
-  return key + c * 0x9E3779B97F4A7C15ull;
+  return key + c * kCtrMul;
+}
+// The word is linear in t modulo 2^64 while (t << 4) | k stays below 2^32 (t < 2^28, k < 16; kJiggleT is the last such
+// t): hash_ctr_word(key, lane, t + n, k) = hash_ctr_word(key, lane, t, k) + n * kCtrStepInc.  A loop over steps forms
+// its per-thread base word (hash_ctr_base) once and adds (tests/test_ctr_recurrence.py).
+constexpr uint64_t kCtrStepInc = 16ull * kCtrMul;
+// low = (t0 << 4) | k, the word's low 32 counter bits
+__device__ __forceinline__ uint64_t hash_ctr_base(uint64_t key, uint64_t lane, uint32_t low) {
+  return key + ((lane << 32) | (uint64_t)low) * kCtrMul;
 }
 __device__ __forceinline__ uint64_t hash_ctr(uint64_t key, uint64_t lane, uint64_t t, uint64_t k) {
   return mix64(hash_ctr_word(key, lane, t, k));

@@ -537,9 +537,18 @@ struct MlpPair {
   }
 };
 
-struct alignas(16) PairScratch {
+struct alignas(16) PairScratchBase {
   float h1[2][kHidden];  // per half: layer-1 output; the env state when it differs from the input
   float x[2][32];        // per half: policy input (+ the 1 of the folded bias column)
+};
+// kDump: a slot per thread that is written and never read, in thread t's own bank (the x write of the threads that hold
+// no input column: rollout_pair_kernel, FDR_PAIR_X_DUMP)
+template <bool kDump>
+struct PairScratch : PairScratchBase {};
+template <>
+struct alignas(16) PairScratch<true> : PairScratchBase {
+  float dump[2][32];
+  __device__ __forceinline__ float* dump_slot(int hh, int t) { return &dump[hh][t]; }
 };
 
 template <int K>

@@ -6,21 +6,46 @@
 
 namespace fdr {
 
-// Where the continuous step loop sits in memory.  The code ahead of the loop is padded to a 64-byte boundary plus
-// FDR_STEP_LOOP_PAD one-dword nops (executed once per wave); with the 12 bytes of loop set-up the compiler puts behind
-// them the loop's first instruction then lies 8 bytes past a 64-byte boundary.  Measured: the same
-// 1,203 instructions run ~0.9 % faster when the loop starts on an 8-byte boundary than 4 bytes off one, which is where
-// it fell before; tools/prologue_mix.py prints the address.  -DFDR_STEP_LOOP_PAD=-1: no padding (make variant).
-#ifndef FDR_STEP_LOOP_PAD
-#define FDR_STEP_LOOP_PAD 15
+// The draw batch's counter word by addition.  hash_ctr_word is linear in the step modulo 2^64, so
+// the word of the batch drawn ahead is the previous batch's plus kStepsPerBatch * 16 * kCtrMul: one 64-bit add per batch
+// in place of the shift, or, two 32-bit products, 64-bit multiply-add and add3 that form it from (lane, step, dim).  Every
+// draw keeps its bits (tests/test_ctr_recurrence.py).  Off by default: measured -0.55 % per FD step on its own, but
+// +0.15 to +0.25 % on top of FDR_PAIR_X_DUMP on two machines (profiles/p26_pair_ctr_xdump.txt) -- the integer multiplies
+// issue at the rate of the 64-bit add (tools/probes/mix_probe.hip).  -DFDR_PAIR_CTR_ADD=1: the variant build.
+#ifndef FDR_PAIR_CTR_ADD
+#define FDR_PAIR_CTR_ADD 0
 #endif
-#if FDR_STEP_LOOP_PAD >= 0
+// The x hand-off write without its select (continuous instances without observation normalisation, where the policy
+// input is the env state itself).  The columns >= NIN of a half's x row (the 1 of the folded bias column, zeros) never
+// change: they are written once ahead of the loop, and in the loop thread t >= NIN stores to its own dump slot of the
+// wave's scratch, which nobody reads -- the address is a per-thread value fixed before the loop, the store's data is s'
+// itself.  -DFDR_PAIR_X_DUMP=0: the select in front of every step's write.
+#ifndef FDR_PAIR_X_DUMP
+#define FDR_PAIR_X_DUMP 1
+#endif
+
+// Where the continuous step loop sits in memory.  The code ahead of the loop is padded to a 64-byte boundary plus a
+// count of one-dword nops (executed once per wave); with the loop set-up the compiler puts behind them the loop's first
+// instruction then lies 8 bytes past a 64-byte boundary.  Measured: the same 1,203 instructions run
+// ~0.9 % faster when the loop starts on an 8-byte boundary than 4 bytes off one, which is where it fell before;
+// tools/prologue_mix.py prints the address.  The set-up's size follows what the loop carries in, so the count depends
+// on the two macros above: FDR_STEP_LOOP_PAD_DUMP for the instances with the select-free x write, FDR_STEP_LOOP_PAD_SEL
+// for those that keep the select (tuned, like the parent's 15, on <17,6,false,0>).  -DFDR_STEP_LOOP_PAD=n sets both,
+// n = -1: no padding (make variant).
+#ifdef FDR_STEP_LOOP_PAD
+#define FDR_STEP_LOOP_PAD_SEL FDR_STEP_LOOP_PAD
+#define FDR_STEP_LOOP_PAD_DUMP FDR_STEP_LOOP_PAD
+#elif FDR_PAIR_CTR_ADD
+#define FDR_STEP_LOOP_PAD_SEL 13
+#define FDR_STEP_LOOP_PAD_DUMP 2
+#else
+#define FDR_STEP_LOOP_PAD_SEL 15
+#define FDR_STEP_LOOP_PAD_DUMP 4
+#endif
 #define FDR_STR2(x) #x
 #define FDR_STR(x) FDR_STR2(x)
-#define FDR_STEP_LOOP_PLACED asm volatile(".p2align 6\n\t.rept " FDR_STR(FDR_STEP_LOOP_PAD) "\n\ts_nop 0\n\t.endr");
-#else
-#define FDR_STEP_LOOP_PLACED
-#endif
+#define FDR_STEP_LOOP_PLACED(n) \
+  if constexpr ((n) >= 0) asm volatile(".p2align 6\n\t.rept " FDR_STR(n) "\n\ts_nop 0\n\t.endr");
 
 // FEAT (fdr_mlp.h): kFeatStates: record visited observations; kFeatObsNorm: observation normalisation (kFeatObsStats,
 // the Welford statistics, runs on rollout_kernel); kFeatTerm: terminating synthetic env -- each half keeps a done flag
@@ -34,7 +59,8 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
   constexpr int MKS = NMK % 8 == 0 ? NMK + 4 : NMK;
   __shared__ float4 env4[NIN * MKS / 4];
   __shared__ float4 wtile[kPairWaves * Lane::kTileF4];
-  __shared__ PairScratch scratch[kPairWaves];
+  constexpr bool kXDump = FDR_PAIR_X_DUMP && !DISC && !(FEAT & kFeatObsNorm);
+  __shared__ PairScratch<kXDump> scratch[kPairWaves];
   float* envMK = reinterpret_cast<float*>(env4);
   for (int e = threadIdx.x; e < NIN * MKS; e += blockDim.x) {
     const int i = e / MKS, k = e % MKS;
@@ -97,6 +123,12 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
   float* h1s = sc->h1[hh];
   const float* mrow = envMK + ji * MKS;
   constexpr bool kSame = !DISC && !norm_obs;
+  static_assert(!kXDump || kSame, "the select-free x write stores s itself");
+  [[maybe_unused]] float* xw = xs + t;  // kXDump: where this thread's x write goes
+  if constexpr (kXDump) {
+    xs[t] = t < NIN ? s : (t == NIN ? 1.f : 0.f);  // the constant columns, once
+    xw = t < NIN ? xs + t : sc->dump_slot(hh, t);
+  }
   typename Lane::L1Rows l1rows;
   pl.l1_prefetch(l1rows, mrow);
   float kr[DISC ? 1 : NA];  // K row t: loop-invariant, kept in VGPRs
@@ -125,12 +157,23 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
   // running batch -- its first four and its last (draw(st) = parts 0 .. 4 in order; the state between parts is dz,
   // then du1 / du2)
   int dctr = ((t / kDrawsPerStep) << 4) | (t % kDrawsPerStep);  // counter word bits of (step offset, dim)
+  // FDR_PAIR_CTR_ADD: the counter word of batch 0's draw (step t / k, dim t % k); each draw_part(0) moves it on a batch
+  [[maybe_unused]] uint64_t dword = 0;
+  if constexpr (FDR_PAIR_CTR_ADD && !DISC) dword = hash_ctr_base(key, ulane, (uint32_t)dctr);
+  [[maybe_unused]] constexpr uint64_t kBatchInc = (uint64_t)kStepsPerBatch * kCtrStepInc;
   uint64_t dz = 0;
   float du1 = 0.f, du2 = 0.f;
   auto draw_part = [&](int k, int st) {
     if (k == 0) {
+#if FDR_PAIR_CTR_ADD
+      // batches come in order from kStepsPerBatch on: st is the step the running word reaches here
+      asm volatile("" : "+v"(dword)::"memory");
+      dword += kBatchInc;
+      dz = mix64_a(dword);
+#else
       asm volatile("" : "+v"(dctr)::"memory");
-      dz = mix64_a(key + (((uint64_t)ulane << 32) | (uint64_t)((st << 4) + dctr)) * 0x9E3779B97F4A7C15ull);
+      dz = mix64_a(key + (((uint64_t)ulane << 32) | (uint64_t)((st << 4) + dctr)) * kCtrMul);
+#endif
     } else if (k == 1) {
       asm volatile("" : "+v"(dz)::"memory");
       dz = mix64_b(dz);
@@ -155,7 +198,8 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
       if (t < NIN && active && (!kTerm || alive_me())) a.states[((int64_t)lane * T + st) * NIN + t] = s;
     }
     float pre = 0.f;
-    xs[t] = t < NIN ? policy_input(s) : (t == NIN ? 1.f : 0.f);
+    if constexpr (kXDump) *xw = s;
+    else xs[t] = t < NIN ? policy_input(s) : (t == NIN ? 1.f : 0.f);
     if constexpr (!kSame) h1s[t] = t < NIN ? s : 0.f;
     wave_lds_sync();
     typename Lane::SIn sin;
@@ -232,7 +276,11 @@ __global__ __launch_bounds__(64 * kPairWaves, 2) void rollout_pair_kernel(Rollou
       // is never used)
       int st = 0;
       draw(0);
-      FDR_STEP_LOOP_PLACED
+      if constexpr (kXDump) {
+        FDR_STEP_LOOP_PLACED(FDR_STEP_LOOP_PAD_DUMP)
+      } else {
+        FDR_STEP_LOOP_PLACED(FDR_STEP_LOOP_PAD_SEL)
+      }
       for (; st + kStepsPerBatch <= T; st += kStepsPerBatch) {
         asm volatile("" ::: "memory");
         mark(-1, s);

@@ -496,7 +496,9 @@ int64_t fdr_fd_grad_fused_counter_bytes(int32_t n_dirs, int64_t n_params) {
 
 int64_t fdr_fd_grad_fused_out_len(int32_t mode, int64_t n_params, int32_t n_all) {
   if (n_params <= 0) return -1;
-  if (mode == FDR_WEIGHT_ZSCORE || mode == FDR_WEIGHT_CENTERED_RANK || mode == FDR_WEIGHT_ZSCORE_MIX) return n_params;
+  if (mode == FDR_WEIGHT_ZSCORE || mode == FDR_WEIGHT_CENTERED_RANK || mode == FDR_WEIGHT_ZSCORE_MIX ||
+      mode == FDR_WEIGHT_TOP_DIRS)
+    return n_params;
   if (mode == FDR_WEIGHT_MOMENTS) return n_all > 0 ? 2 * n_params + 1 + n_all : -1;
   return -1;
 }
@@ -519,18 +521,29 @@ static int opt_call(int32_t kind, double lr, double beta1, double beta2, double 
   return opt_validate(kind, o->h, step, state0, state1);
 }
 
+// the top-b arguments every FDR_WEIGHT_TOP_DIRS entry shares (lanes_per_dir >= 1 and the lane range checked before)
+static int top_dirs_validate(int32_t n_all, int32_t lanes_per_dir, int32_t top_dirs, int32_t lane_lo, int32_t n_local) {
+  if (n_all % lanes_per_dir != 0) return set_error(FDR_ERR_INVALID, "n_all is not a multiple of lanes_per_dir");
+  if (top_dirs < 1) return set_error(FDR_ERR_INVALID, "top_dirs < 1");
+  if (top_dirs > n_all / lanes_per_dir) return set_error(FDR_ERR_INVALID, "top_dirs above the n_all / lanes_per_dir directions");
+  if (lane_lo % lanes_per_dir != 0 || n_local % lanes_per_dir != 0)
+    return set_error(FDR_ERR_INVALID, "lane_lo / n_local is not a multiple of lanes_per_dir");
+  return FDR_OK;
+}
+
 static int fd_grad_fused_impl(const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
                               int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
                               int32_t lane_lo, const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir,
                               float sigma, int32_t mode, double* out, float* theta, double lr, double lr_scale,
                               float* hist, double* dsgd_out, void* workspace, int64_t workspace_bytes,
-                              fdr_stream stream, const MixChannels* mix = nullptr, const OptCall* opt = nullptr) {
+                              fdr_stream stream, const MixChannels* mix = nullptr, const OptCall* opt = nullptr,
+                              int32_t top_dirs = 0) {
   if (!table || !out || n_params <= 0 || table_size < n_params || n_dirs < 0)
     return set_error(FDR_ERR_INVALID, "bad arguments");
   if (mode == FDR_WEIGHT_ZSCORE_MIX && !mix)
     return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_grad_fused_mix / fdr_fd_step_mix");
   if (mode != FDR_WEIGHT_ZSCORE && mode != FDR_WEIGHT_CENTERED_RANK && mode != FDR_WEIGHT_MOMENTS &&
-      mode != FDR_WEIGHT_ZSCORE_MIX)
+      mode != FDR_WEIGHT_ZSCORE_MIX && mode != FDR_WEIGHT_TOP_DIRS)
     return set_error(FDR_ERR_INVALID, "unknown weighting mode");
   if (lanes_per_dir < 1) return set_error(FDR_ERR_INVALID, "lanes_per_dir < 1");
   if (n_dirs == 0) return set_error(FDR_ERR_INVALID, "no directions (DSGD would divide by ||g|| = 0)");
@@ -538,8 +551,13 @@ static int fd_grad_fused_impl(const float* table, int64_t table_size, const int6
   if (!idx_local || (!rewards_all && !mix) || !sign_local || !norm2_local)
     return set_error(FDR_ERR_INVALID, "NULL pointer");
   if (n_all <= 0 || lane_lo < 0 || lane_lo + n_local > n_all) return set_error(FDR_ERR_INVALID, "bad lane range");
+  if (mode == FDR_WEIGHT_TOP_DIRS) {
+    const int rc = top_dirs_validate(n_all, lanes_per_dir, top_dirs, lane_lo, n_local);
+    if (rc) return rc;
+  }
   FusedCall c{};
   if (mix) c.mix = *mix;
+  c.top_dirs = top_dirs;
   c.fd.table = table;
   c.fd.max_idx = table_size - n_params;
   c.fd.idx = idx_local;
@@ -578,6 +596,8 @@ int fdr_fd_grad_fused(fdr_ctx* ctx, const float* table, int64_t table_size, cons
   FDR_CTX(ctx, C);
   if (mode == FDR_WEIGHT_ZSCORE_MIX)
     return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_grad_fused_mix / fdr_fd_step_mix");
+  if (mode == FDR_WEIGHT_TOP_DIRS)
+    return set_error(FDR_ERR_INVALID, "top-b selection takes fdr_fd_grad_fused_top / fdr_fd_step_top");
   const int64_t need = fdr_fd_grad_fused_out_len(mode, n_params, n_all);
   if (need > 0 && out_len < need) return set_error(FDR_ERR_INVALID, "out_len below fdr_fd_grad_fused_out_len");
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, lane_lo,
@@ -595,6 +615,8 @@ int fdr_fd_step(fdr_ctx* ctx, const float* table, int64_t table_size, const int6
   if (mode == FDR_WEIGHT_MOMENTS) return set_error(FDR_ERR_INVALID, "fdr_fd_step takes z-score or centred-rank weights");
   if (mode == FDR_WEIGHT_ZSCORE_MIX)
     return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_grad_fused_mix / fdr_fd_step_mix");
+  if (mode == FDR_WEIGHT_TOP_DIRS)
+    return set_error(FDR_ERR_INVALID, "top-b selection takes fdr_fd_grad_fused_top / fdr_fd_step_top");
   if (n_all != n_dirs * lanes_per_dir) return set_error(FDR_ERR_INVALID, "fdr_fd_step is single-process: n_all = n_local");
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, 0,
                             sign_local, norm2_local, lanes_per_dir, sigma, mode, g, theta, lr, lr_scale, theta_hist,
@@ -671,6 +693,7 @@ int fdr_fd_step_opt(fdr_ctx* ctx, const float* table, int64_t table_size, const 
   if (mode == FDR_WEIGHT_MOMENTS)
     return set_error(FDR_ERR_INVALID, "fdr_fd_step_opt takes z-score or centred-rank weights");
   if (mode == FDR_WEIGHT_ZSCORE_MIX) return set_error(FDR_ERR_INVALID, "the mixed objective takes fdr_fd_step_mix_opt");
+  if (mode == FDR_WEIGHT_TOP_DIRS) return set_error(FDR_ERR_INVALID, "top-b selection takes fdr_fd_step_top_opt");
   if (n_all != n_dirs * lanes_per_dir)
     return set_error(FDR_ERR_INVALID, "fdr_fd_step_opt is single-process: n_all = n_local");
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, 0,
@@ -701,6 +724,73 @@ int fdr_fd_step_mix_opt(fdr_ctx* ctx, const float* table, int64_t table_size, co
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, mx.v[0], n_all, mx.p[0], 0, sign_local,
                             norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_ZSCORE_MIX, g, theta, 0.0, 0.0, theta_hist,
                             out, workspace, workspace_bytes, stream, &mx, &o);
+}
+
+int64_t fdr_top_dir_weights_workspace_bytes(int32_t n_all) { return top_dirs_workspace_bytes(n_all); }
+
+int fdr_top_dir_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, double policy_reward,
+                        int32_t lanes_per_dir, int32_t top_dirs, int32_t lane_lo, int32_t n_local, double* w,
+                        int8_t* selected, void* workspace, int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (!rewards_all || n_all <= 0 || lanes_per_dir < 1 || lane_lo < 0 || n_local < 0 || lane_lo + n_local > n_all)
+    return set_error(FDR_ERR_INVALID, "bad arguments");
+  const int rc = top_dirs_validate(n_all, lanes_per_dir, top_dirs, lane_lo, n_local);
+  if (rc) return rc;
+  if (n_local == 0) return FDR_OK;
+  if (!w) return set_error(FDR_ERR_INVALID, "NULL w");
+  return launch_top_dir_weights(rewards_all, n_all, policy_reward, lanes_per_dir, top_dirs, lane_lo, n_local, w,
+                                selected, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int64_t fdr_fd_grad_fused_top_workspace_bytes(int32_t n_dirs, int32_t lanes_per_dir, int64_t n_params, int32_t n_all) {
+  if (lanes_per_dir < 1) return -1;
+  return fused_top_workspace_bytes(n_dirs, n_dirs * lanes_per_dir, n_params, n_all);
+}
+
+int fdr_fd_grad_fused_top(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local,
+                          int32_t n_dirs, int64_t n_params, const double* rewards_all, int32_t n_all,
+                          double policy_reward, int32_t lane_lo, const int8_t* sign_local, const double* norm2_local,
+                          int32_t lanes_per_dir, float sigma, int32_t top_dirs, double* out, int64_t out_len,
+                          void* workspace, int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (n_params > 0 && out_len < n_params) return set_error(FDR_ERR_INVALID, "out_len below fdr_fd_grad_fused_out_len");
+  return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, lane_lo,
+                            sign_local, norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_TOP_DIRS, out, nullptr, 0.0, 0.0,
+                            nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, top_dirs);
+}
+
+int fdr_fd_step_top(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                    int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
+                    const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                    int32_t top_dirs, float* theta, double lr, double lr_scale, double* g, float* theta_hist,
+                    double* out, void* workspace, int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (!theta || !g || !out) return set_error(FDR_ERR_INVALID, "NULL theta / g / out");
+  if (n_all != n_dirs * lanes_per_dir)
+    return set_error(FDR_ERR_INVALID, "fdr_fd_step_top is single-process: n_all = n_local");
+  return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, 0,
+                            sign_local, norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_TOP_DIRS, g, theta, lr, lr_scale,
+                            theta_hist, out, workspace, workspace_bytes, stream, nullptr, nullptr, top_dirs);
+}
+
+int fdr_fd_step_top_opt(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                        int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
+                        const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                        int32_t top_dirs, float* theta, int32_t kind, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, double momentum, double dampening, int32_t nesterov, int64_t step,
+                        float* state0, float* state1, double* g, float* theta_hist, double* out, void* workspace,
+                        int64_t workspace_bytes, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  OptCall o;
+  const int rc = opt_call(kind, lr, beta1, beta2, eps, weight_decay, momentum, dampening, nesterov, step, state0,
+                          state1, &o);
+  if (rc) return rc;
+  if (!theta || !g || !out) return set_error(FDR_ERR_INVALID, "NULL theta / g / out");
+  if (n_all != n_dirs * lanes_per_dir)
+    return set_error(FDR_ERR_INVALID, "fdr_fd_step_top_opt is single-process: n_all = n_local");
+  return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, 0,
+                            sign_local, norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_TOP_DIRS, g, theta, 0.0, 0.0,
+                            theta_hist, out, workspace, workspace_bytes, stream, nullptr, &o, top_dirs);
 }
 
 int fdr_rank_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, int32_t lane_lo, int32_t n_local,

@@ -1,5 +1,5 @@
 // Internal (non-ABI) host interface of the learner-side units behind the C ABI (fdr_api.hip): the launchers and
-// workspace queries of fdr_learner.hip, fdr_learner_fused.hip, fdr_dsgd.hip, fdr_optim.hip, fdr_novelty.hip and
+// workspace queries of fdr_learner.hip, fdr_learner_fused.hip, fdr_top_dirs.hip, fdr_dsgd.hip, fdr_optim.hip, fdr_novelty.hip and
 // fdr_mlp_vbn.hip, and the two structs that cross to their kernels by value (LambdaRow, FdArgs).
 #pragma once
 #include "fdr_internal.h"
@@ -108,6 +108,7 @@ struct FusedCall {
   FdArgs fd;             // table .. sigma and out
   int mode;              // FDR_WEIGHT_*
   MixChannels mix;       // FDR_WEIGHT_ZSCORE_MIX only
+  int top_dirs;          // FDR_WEIGHT_TOP_DIRS only: b, the directions kept (1 <= b <= n_all / lpd)
   // fdr_fd_step: DSGD in the same call (theta NULL: the gradient only)
   float* theta;
   double lr, lr_scale;
@@ -123,6 +124,16 @@ int64_t fused_workspace_bytes(int n_dirs, int n_local, int64_t P, int mode);
 int64_t fused_counter_bytes(int n_dirs, int64_t P);
 int launch_fd_grad_fused(const FusedCall& c, void* ws, int64_t ws_bytes, hipStream_t stream);
 int launch_rank_weights(const double* r_all, int n_all, int lo, int n_local, double* w, hipStream_t stream);
+// FDR_WEIGHT_TOP_DIRS: fused_workspace_bytes(.., FDR_WEIGHT_CENTERED_RANK) and, behind it, the lane mask over all ranks
+int64_t fused_top_workspace_bytes(int n_dirs, int n_local, int64_t P, int n_all);
+
+// ---- fdr_top_dirs.hip ----
+// top-b direction selection: top_dirs_select_kernel (lane mask over ALL n_all lanes -> ws) + top_dirs_weights_kernel
+// (w [n_local], selected int8 [n_local / lpd] or NULL).  ws: top_dirs_workspace_bytes(n_all).  The caller has
+// validated n_all % lpd == 0, 1 <= top_dirs <= n_all / lpd, lo and n_local multiples of lpd inside [0, n_all].
+int64_t top_dirs_workspace_bytes(int n_all);
+int launch_top_dir_weights(const double* r_all, int n_all, double pr, int lpd, int top_dirs, int lo, int n_local,
+                           double* w, int8_t* selected, void* ws, int64_t ws_bytes, hipStream_t stream);
 
 // ---- fdr_dsgd.hip ----
 int64_t dsgd_workspace_bytes(int64_t P);

@@ -1,7 +1,7 @@
 // fdr_learner_fused.hip -- the fused learner step: weighting, noise-weighted gradient and chunk combine in one launch
 // (fd_grad_fused_kernel; fd_grad_fused_mix_kernel for the reward / novelty / entropy objective), the DSGD that can
 // follow it in the same call (dsgd_apply_cb_kernel; fdr_optim.hip's opt_apply_cb_kernel for Adam / AdamW / SGD),
-// centred-rank weights.
+// centred-rank weights.  Top-b direction weights: fdr_top_dirs.hip, in front of the centred-rank instance.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -592,6 +592,7 @@ static GradPlan fused_plan(int n_dirs, int64_t P) {
 }
 
 // workspace: [counters: col_blocks + 1 u32, padded to 256 B][gsq][update partials][rank weights][partial slabs]
+// (FDR_WEIGHT_TOP_DIRS: [lane mask, n_all bytes] behind them)
 static int64_t pad256(int64_t b) { return (b + 255) / 256 * 256; }
 int64_t fused_counter_bytes(int n_dirs, int64_t P) {
   const GradPlan f = fused_plan(std::max(1, n_dirs), P);
@@ -605,12 +606,21 @@ int64_t fused_workspace_bytes(int n_dirs, int n_local, int64_t P, int mode) {
          pad256((int64_t)std::max(0, n_local) * 8) + slabs;
 }
 
+// FDR_WEIGHT_TOP_DIRS: the centred-rank layout (its weight region holds the top-b weights), then the lane mask
+int64_t fused_top_workspace_bytes(int n_dirs, int n_local, int64_t P, int n_all) {
+  const int64_t base = fused_workspace_bytes(n_dirs, n_local, P, FDR_WEIGHT_CENTERED_RANK);
+  const int64_t mask = top_dirs_workspace_bytes(n_all);
+  return base < 0 || mask < 0 ? -1 : base + mask;
+}
+
 int launch_fd_grad_fused(const FusedCall& c, void* ws, int64_t ws_bytes, hipStream_t stream) {
   FdArgs a = c.fd;
   const int64_t P = a.P;
   const int n_local = a.n_dirs * a.lpd;
-  if (!ws || ws_bytes < fused_workspace_bytes(a.n_dirs, n_local, P, c.mode))
-    return set_error(FDR_ERR_WORKSPACE, "fd_grad_fused workspace too small");
+  const bool top = c.mode == FDR_WEIGHT_TOP_DIRS;
+  const int64_t need = top ? fused_top_workspace_bytes(a.n_dirs, n_local, P, a.n_all)
+                           : fused_workspace_bytes(a.n_dirs, n_local, P, c.mode);
+  if (!ws || ws_bytes < need) return set_error(FDR_ERR_WORKSPACE, "fd_grad_fused workspace too small");
   const GradPlan f = fused_plan(a.n_dirs, P);
   char* w = static_cast<char*>(ws);
   const int64_t cnt_b = fused_counter_bytes(a.n_dirs, P);
@@ -642,6 +652,14 @@ int launch_fd_grad_fused(const FusedCall& c, void* ws, int64_t ws_bytes, hipStre
     case FDR_WEIGHT_ZSCORE_MIX:
       hipLaunchKernelGGL(fd_grad_fused_mix_kernel, grid, dim3(256), 0, stream, FdMixArgs{a, c.mix});
       break;
+    case FDR_WEIGHT_TOP_DIRS: {  // the top-b weights into the weight region, then the instance that takes weights
+      const int64_t mask_off = fused_workspace_bytes(a.n_dirs, n_local, P, FDR_WEIGHT_CENTERED_RANK);
+      const int rc = launch_top_dir_weights(a.r_all, a.n_all, a.pr, a.lpd, c.top_dirs, a.lo, n_local,
+                                            const_cast<double*>(a.w), nullptr, w + mask_off, ws_bytes - mask_off, stream);
+      if (rc) return rc;
+      hipLaunchKernelGGL(fd_grad_fused_kernel<FDR_WEIGHT_CENTERED_RANK>, grid, dim3(256), 0, stream, a);
+      break;
+    }
     default:
       return set_error(FDR_ERR_INVALID, "unknown weighting mode");
   }

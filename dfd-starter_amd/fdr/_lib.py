@@ -18,6 +18,7 @@ FDR_ROLLOUT_PAIR, FDR_ROLLOUT_SINGLE, FDR_ROLLOUT_AUTO, FDR_ROLLOUT_WIDE = 0, 1,
 FDR_ROLLOUT_GENERIC = 4   # the runtime-shaped kernel family at every shape
 FDR_WEIGHT_ZSCORE, FDR_WEIGHT_CENTERED_RANK, FDR_WEIGHT_MOMENTS = 0, 1, 2
 FDR_WEIGHT_ZSCORE_MIX = 3   # reward / novelty / entropy: fdr_fd_grad_fused_mix, fdr_fd_step_mix
+FDR_WEIGHT_TOP_DIRS = 4     # top-b directions (ARS): fdr_top_dir_weights, fdr_fd_grad_fused_top, fdr_fd_step_top[_opt]
 FDR_OPT_ADAM, FDR_OPT_ADAMW, FDR_OPT_SGD = 1, 2, 3   # fdr_opt_step, fdr_fd_step_opt, fdr_fd_step_mix_opt
 FDR_LOADER_LANE, FDR_LOADER_PAIR, FDR_LOADER_DYN = 0, 1, 2   # include/fdr_diag.h
 
@@ -41,7 +42,8 @@ EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy",
            "fdr_atari_strategies", "fdr_atari_bn_refresh_workspace_bytes", "fdr_atari_bn_refresh",
            "fdr_diag_theta_prime", "fdr_fd_grad_fused_mix", "fdr_fd_step_mix", "fdr_fd_weights_mix",
            "fdr_opt_workspace_bytes", "fdr_opt_step", "fdr_fd_step_opt", "fdr_fd_step_mix_opt", "fdr_noise_fill",
-           "fdr_rollout_episodes")
+           "fdr_rollout_episodes", "fdr_top_dir_weights_workspace_bytes", "fdr_top_dir_weights",
+           "fdr_fd_grad_fused_top_workspace_bytes", "fdr_fd_grad_fused_top", "fdr_fd_step_top", "fdr_fd_step_top_opt")
 
 
 class FDRError(RuntimeError):
@@ -165,6 +167,16 @@ def _load():
         "fdr_fd_step_mix_opt": (ctypes.c_int, [P, P, I64, P, I32, I64, P, P, P, I32, F64, F64, F64, F64, F64, F64, P, P,
                                                I32, F32, P, I32, F64, F64, F64, F64, F64, F64, F64, I32, I64, P, P, P, P,
                                                P, P, I64, P]),
+        # fdr_fd_grad_fused / fdr_fd_step / fdr_fd_step_opt with top_dirs in mode's place
+        "fdr_top_dir_weights_workspace_bytes": (I64, [I32]),
+        "fdr_top_dir_weights": (ctypes.c_int, [P, P, I32, F64, I32, I32, I32, I32, P, P, P, I64, P]),
+        "fdr_fd_grad_fused_top_workspace_bytes": (I64, [I32, I32, I64, I32]),
+        "fdr_fd_grad_fused_top": (ctypes.c_int, [P, P, I64, P, I32, I64, P, I32, F64, I32, P, P, I32, F32, I32, P, I64,
+                                                 P, I64, P]),
+        "fdr_fd_step_top": (ctypes.c_int, [P, P, I64, P, I32, I64, P, I32, F64, P, P, I32, F32, I32, P, F64, F64, P, P,
+                                           P, P, I64, P]),
+        "fdr_fd_step_top_opt": (ctypes.c_int, [P, P, I64, P, I32, I64, P, I32, F64, P, P, I32, F32, I32, P, I32, F64,
+                                               F64, F64, F64, F64, F64, F64, I32, I64, P, P, P, P, P, P, I64, P]),
         "fdr_dsgd_step_ex": (ctypes.c_int, [P, P, P, I32, I64, F64, F64, P, P, P, I64, P]),
         "fdr_dsgd_step": (ctypes.c_int, [P, P, P, I64, F64, F64, P, P, I64, P]),
         "fdr_atari_env_frames": (ctypes.c_int, [ctypes.c_uint64, I64, I32, I32, P, P]),

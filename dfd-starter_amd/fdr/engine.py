@@ -317,8 +317,9 @@ _WS_ZERO_PREFIX = {}
 _FUSED_SIZES = {}
 
 
-def _fused_workspace(mode, n_dirs, lanes_per_dir, n_params, device):
-    """The fdr_fd_grad_fused / fdr_fd_step workspace with its ticket-counter prefix guaranteed zero.
+def _fused_workspace(mode, n_dirs, lanes_per_dir, n_params, device, n_all=None):
+    """The fdr_fd_grad_fused / fdr_fd_step workspace with its ticket-counter prefix guaranteed zero (n_all: the
+    FDR_WEIGHT_TOP_DIRS query takes it in mode's place -- its mask covers the lanes of all ranks).
 
     A call leaves exactly its own counter prefix, fdr_fd_grad_fused_counter_bytes(n_dirs, P), at zero; the bytes
     behind it hold that call's slabs / partials.  A later call whose prefix is longer (more column blocks) would
@@ -326,11 +327,16 @@ def _fused_workspace(mode, n_dirs, lanes_per_dir, n_params, device):
     whenever it grows past what is known to be zero."""
     key = ("fused_%d" % mode, device)
     old = _WS.get(key)
-    skey = (mode, n_dirs, int(lanes_per_dir), n_params)
+    skey = (mode, n_dirs, int(lanes_per_dir), n_params, n_all)
     sizes = _FUSED_SIZES.get(skey)
     if sizes is None:  # the library's size queries, once per shape
-        sizes = _FUSED_SIZES[skey] = (lib.fdr_fd_grad_fused_workspace_bytes(n_dirs, int(lanes_per_dir), n_params, mode),
-                                      int(lib.fdr_fd_grad_fused_counter_bytes(n_dirs, n_params)))
+        if mode == _lib.FDR_WEIGHT_TOP_DIRS:
+            nb = lib.fdr_fd_grad_fused_top_workspace_bytes(n_dirs, int(lanes_per_dir), n_params, int(n_all))
+        else:
+            nb = lib.fdr_fd_grad_fused_workspace_bytes(n_dirs, int(lanes_per_dir), n_params, mode)
+        if nb < 0:
+            raise ValueError("fused workspace query: bad n_dirs / lanes_per_dir / P / n_all")
+        sizes = _FUSED_SIZES[skey] = (nb, int(lib.fdr_fd_grad_fused_counter_bytes(n_dirs, n_params)))
     nb, cb = sizes
     ws = _workspace(key[0], nb, device, zeroed=True)
     if ws is not old:
@@ -472,6 +478,57 @@ def rank_weights(rewards_all, lane_lo, n_local):
     return w
 
 
+def top_dir_weights(rewards_all, policy_reward, lanes_per_dir, top_dirs, lane_lo, n_local, selected=False):
+    """Top-b direction weights (fdr_top_dir_weights) of lanes [lane_lo, lane_lo + n_local): the top_dirs best
+    directions by the maximum of their lanes_per_dir returns keep their lanes, z-scored over the kept lanes; 0.0
+    elsewhere.  -> w f64 [n_local], or (w, selected int8 [n_local / lanes_per_dir]) with selected=True."""
+    _check_dev(rewards_all)
+    dev = rewards_all.device
+    w = torch.empty(n_local, dtype=torch.float64, device=dev)
+    sel = torch.empty(n_local // max(1, int(lanes_per_dir)), dtype=torch.int8, device=dev) if selected else None
+    ws = _workspace("top_dirs", max(0, lib.fdr_top_dir_weights_workspace_bytes(rewards_all.numel())), dev)
+    check(lib.fdr_top_dir_weights(_c(dev), _p(rewards_all), rewards_all.numel(), float(policy_reward),
+                                  int(lanes_per_dir), int(top_dirs), int(lane_lo), int(n_local), _p(w), _p(sel), _p(ws),
+                                  ws.numel(), _stream(dev)), "fdr_top_dir_weights")
+    return (w, sel) if selected else w
+
+
+def fd_grad_fused_top(table, idx_local, rewards_all, policy_reward, lane_lo, sign_local, norm2_local, lanes_per_dir,
+                      sigma, n_params, top_dirs, out=None):
+    """fd_grad_fused with the top-b direction weights (fdr_fd_grad_fused_top): top_dirs of the n_all / lanes_per_dir
+    directions of rewards_all (all ranks' lanes) are kept.  -> g f64 [P]."""
+    _check_dev(table, idx_local, rewards_all, sign_local, norm2_local)
+    dev = table.device
+    n_dirs = idx_local.numel() // int(lanes_per_dir)
+    if out is None:
+        out = torch.empty(n_params, dtype=torch.float64, device=dev)
+    ws = _fused_workspace(_lib.FDR_WEIGHT_TOP_DIRS, n_dirs, lanes_per_dir, n_params, dev, n_all=rewards_all.numel())
+    check(lib.fdr_fd_grad_fused_top(_c(dev), _p(table), table.numel(), _p(idx_local), n_dirs, n_params,
+                                    _p(rewards_all), rewards_all.numel(), float(policy_reward), int(lane_lo),
+                                    _p(sign_local), _p(norm2_local), int(lanes_per_dir), float(sigma), int(top_dirs),
+                                    _p(out), out.numel(), _p(ws), ws.numel(), _stream(dev)), "fdr_fd_grad_fused_top")
+    return out
+
+
+def fd_step_top(table, idx_local, rewards, policy_reward, sign_local, norm2_local, lanes_per_dir, sigma, theta, lr,
+                lr_scale, top_dirs, g=None, out=None, theta_hist=None):
+    """fd_step with the top-b direction weights (fdr_fd_step_top).  Returns device f64[2] = (||d theta||, ||grad||)."""
+    _check_dev(table, idx_local, rewards, sign_local, norm2_local, theta, g, theta_hist)
+    dev = table.device
+    P = theta.numel()
+    n_dirs = idx_local.numel() // int(lanes_per_dir)
+    if g is None:
+        g = torch.empty(P, dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = _fused_workspace(_lib.FDR_WEIGHT_TOP_DIRS, n_dirs, lanes_per_dir, P, dev, n_all=rewards.numel())
+    check(lib.fdr_fd_step_top(_c(dev), _p(table), table.numel(), _p(idx_local), n_dirs, P, _p(rewards), rewards.numel(),
+                              float(policy_reward), _p(sign_local), _p(norm2_local), int(lanes_per_dir), float(sigma),
+                              int(top_dirs), _p(theta), float(lr), float(lr_scale), _p(g), _p(theta_hist), _p(out),
+                              _p(ws), ws.numel(), _stream(dev)), "fdr_fd_step_top")
+    return out
+
+
 def dsgd_step_ex(theta, src, moments, lr, lr_scale, g_out=None, out=None):
     """DSGD from g (moments=False) or from summed moments (g = (A - m B) / sd written to g_out)."""
     _check_dev(theta, src, g_out)
@@ -546,6 +603,26 @@ def fd_step_opt(table, idx_local, rewards, policy_reward, sign_local, norm2_loca
                               float(policy_reward), _p(sign_local), _p(norm2_local), int(lanes_per_dir), float(sigma), m,
                               _p(theta), *opt.args(), _p(g), _p(theta_hist), _p(out), _p(ws), ws.numel(), _stream(dev)),
           "fdr_fd_step_opt")
+    return out
+
+
+def fd_step_top_opt(table, idx_local, rewards, policy_reward, sign_local, norm2_local, lanes_per_dir, sigma, theta, opt,
+                    top_dirs, g=None, out=None, theta_hist=None):
+    """fd_step_top with the optimizer's apply launch in DSGD's place (fdr_fd_step_top_opt); opt an OptSpec."""
+    _check_dev(table, idx_local, rewards, sign_local, norm2_local, theta, g, theta_hist)
+    dev = table.device
+    P = theta.numel()
+    opt.check(P, dev)
+    n_dirs = idx_local.numel() // int(lanes_per_dir)
+    if g is None:
+        g = torch.empty(P, dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = _fused_workspace(_lib.FDR_WEIGHT_TOP_DIRS, n_dirs, lanes_per_dir, P, dev, n_all=rewards.numel())
+    check(lib.fdr_fd_step_top_opt(_c(dev), _p(table), table.numel(), _p(idx_local), n_dirs, P, _p(rewards),
+                                  rewards.numel(), float(policy_reward), _p(sign_local), _p(norm2_local),
+                                  int(lanes_per_dir), float(sigma), int(top_dirs), _p(theta), *opt.args(), _p(g),
+                                  _p(theta_hist), _p(out), _p(ws), ws.numel(), _stream(dev)), "fdr_fd_step_top_opt")
     return out
 
 

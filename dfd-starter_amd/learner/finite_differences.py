@@ -17,6 +17,12 @@ instead.
 ``weighting="centred_rank"`` (build extension named by the north star; the reference's weighting is the
 z-score) ranks all returns, so it keeps the all-gather of the per-lane returns + the all-reduce of g.
 
+``weighting="top_directions"`` with ``top_directions=b`` (build extension: the selection of Augmented Random Search)
+keeps the b best directions, ranked by the maximum of their lanes' returns, and z-scores the kept lanes' returns over
+themselves; every other lane weighs 0 (fdr_fd_step_top / fdr_fd_grad_fused_top, fdr_top_dir_weights on the list route,
+where every return is a direction of its own).  An int b >= 1 is clipped to the step's direction count D, a float f in
+(0, 1] means ceil(f D).  It ranks all returns like the centred rank, and takes the same routes.
+
 ``objective="mixed"`` (build extension; the reference carries the combination at finite_differences.py:40-48, switched
 off) weights lane i by (1 - omega) z(r_i - r_pol) + omega z(nov_i - nov_pol) + ent_coef z(ent_i - ent_pol), every
 channel standardised over all lanes, with omega read from ``self.omega`` at the step: fdr_fd_step_mix /
@@ -105,17 +111,62 @@ def describe_optimizer(policy, opt):
     return OptimizerRoute("device", "adamw" if gr.get("decoupled_weight_decay") else "adam")
 
 
+def _check_top_directions(b):
+    """top_directions: an int b >= 1 (directions kept) or a float fraction in (0, 1]."""
+    if b is None:
+        raise ValueError("weighting='top_directions' needs top_directions: an int b >= 1 or a float fraction in (0, 1]")
+    if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)):
+        raise ValueError("top_directions is an int b >= 1 or a float fraction in (0, 1], not %r" % (b,))
+    if isinstance(b, (int, np.integer)):
+        if b < 1:
+            raise ValueError("top_directions as an int is the number of directions kept: >= 1, not %d" % b)
+    elif not (0.0 < b <= 1.0):
+        raise ValueError("top_directions as a float is the fraction of directions kept: in (0, 1], not %r" % (b,))
+
+
+def resolve_top_directions(b, n_dirs):
+    """The directions a step over n_dirs directions keeps: an int clipped to n_dirs (the list route can deliver fewer
+    returns than expected), a float f -> ceil(f n_dirs).  The product is the f64 one, so a fraction that is not a
+    binary number can land just above an integer: 0.07 * 100 = 7.000000000000001 keeps 8 directions, not 7.  Pass an
+    int where the count matters."""
+    _check_top_directions(b)
+    if isinstance(b, (int, np.integer)):
+        return max(1, min(int(b), int(n_dirs)))
+    return max(1, min(int(np.ceil(float(b) * n_dirs)), int(n_dirs)))
+
+
+def parse_weighting(spec):
+    """A command-line weighting -> (weighting, top_directions): "zscore" | "centred_rank" | "top_directions:<b>", b an
+    int (directions kept: "512") or, where it does not read as an int, a float fraction of them ("0.25", "1e-1")."""
+    name, _, b = spec.partition(":")
+    if name != "top_directions":
+        if b:
+            raise ValueError("only top_directions takes a parameter, not %r" % (spec,))
+        return name, None
+    try:
+        top = int(b)
+    except ValueError:
+        top = float(b)      # ValueError for anything that is no number
+    _check_top_directions(top)
+    return name, top
+
+
 class FiniteDifferences(object):
     def __init__(self, policy, gradient_optimizer, omega, noise_source, noise_std=0.1, batch_size=100,
                  ent_coef=0.0, max_delayed_return=10, process_group=None, weighting="zscore", one_collective=True,
-                 objective="reward"):
-        if weighting not in ("zscore", "centred_rank"):
-            raise ValueError("weighting must be 'zscore' (the reference) or 'centred_rank'")
+                 objective="reward", top_directions=None):
+        if weighting not in ("zscore", "centred_rank", "top_directions"):
+            raise ValueError("weighting must be 'zscore' (the reference), 'centred_rank' or 'top_directions'")
         if objective not in ("reward", "mixed"):
             raise ValueError("objective must be 'reward' (the reference's step) or 'mixed'")
         if objective == "mixed" and weighting != "zscore":
-            raise ValueError("objective='mixed' standardises each channel: weighting='centred_rank' is not built for it")
+            raise ValueError("objective='mixed' standardises each channel: weighting=%r is not built for it" % weighting)
+        if weighting == "top_directions":
+            _check_top_directions(top_directions)
+        elif top_directions is not None:
+            raise ValueError("top_directions goes with weighting='top_directions'")
         self.weighting = weighting
+        self.top_directions = top_directions
         self.objective = objective
         self.last_mix = None    # objective="mixed": the (reward, novelty, entropy) coefficients of the latest step
         self._policy_values = (0.0, 0.0, 0.0)   # ... and the policy's own reward, novelty, entropy it subtracted
@@ -274,6 +325,8 @@ class FiniteDifferences(object):
         if self.objective == "mixed":
             return self._step_batch_mixed(b, table)
         P = self.policy.num_params
+        if self.weighting == "top_directions":
+            return self._step_batch_top(b, table, policy_reward)
         if not self._distributed():
             if P <= FUSED_STEP_MAX_P and self.opt_route.route == "device":   # the same two launches, the apply swapped
                 slot = self._hist_slot()
@@ -309,6 +362,37 @@ class FiniteDifferences(object):
         rewards_all, lane_lo = fdist.gather_rewards(b.reward, self.process_group, getattr(b, "rank_lanes", None))
         g = engine.fd_grad_fused(table, b.idx, rewards_all, policy_reward, lane_lo, b.sign, b.norm2,
                                  b.lanes_per_dir, self.noise_std, P, mode=self.weighting, out=self.gradient_memory)
+        fdist.allreduce_grad(g, self.process_group)
+        return self._apply(g)
+
+    def _step_batch_top(self, b, table, policy_reward):
+        """weighting="top_directions": the routes of centred rank -- fd_step_top_opt / fd_step_top (one process,
+        P <= 65536), else fd_grad_fused_top + the apply; sharded, the gather form (the selection ranks the
+        directions of all ranks): one all-gather of the returns, one all-reduce of g."""
+        P = self.policy.num_params
+        lpd = b.lanes_per_dir
+        if not self._distributed():
+            top = resolve_top_directions(self.top_directions, b.reward.numel() // lpd)
+            if P <= FUSED_STEP_MAX_P and self.opt_route.route == "device":
+                slot = self._hist_slot()
+                engine.fd_step_top_opt(table, b.idx, b.reward, policy_reward, b.sign, b.norm2, lpd, self.noise_std,
+                                       self.policy.flat, self._opt_spec(), top, g=self.gradient_memory, out=self._out,
+                                       theta_hist=slot)
+                return self._after_opt(slot)
+            if P <= FUSED_STEP_MAX_P and self.using_dsgd:
+                lr, lr_scale = self._lr()
+                slot = self._hist_slot()
+                engine.fd_step_top(table, b.idx, b.reward, policy_reward, b.sign, b.norm2, lpd, self.noise_std,
+                                   self.policy.flat, lr, lr_scale, top, g=self.gradient_memory, out=self._out,
+                                   theta_hist=slot)
+                return self._after_update(slot)
+            g = engine.fd_grad_fused_top(table, b.idx, b.reward, policy_reward, 0, b.sign, b.norm2, lpd, self.noise_std,
+                                         P, top, out=self.gradient_memory)
+            return self._apply(g)
+        rewards_all, lane_lo = fdist.gather_rewards(b.reward, self.process_group, getattr(b, "rank_lanes", None))
+        top = resolve_top_directions(self.top_directions, rewards_all.numel() // lpd)
+        g = engine.fd_grad_fused_top(table, b.idx, rewards_all, policy_reward, lane_lo, b.sign, b.norm2, lpd,
+                                     self.noise_std, P, top, out=self.gradient_memory)
         fdist.allreduce_grad(g, self.process_group)
         return self._apply(g)
 
@@ -533,6 +617,9 @@ class FiniteDifferences(object):
                 coef = engine.fd_weights_mix(ch_all, self._policy_values, coefs, lane_lo, ones, n2, 1, 1.0)
             elif self.weighting == "centred_rank":   # ranks over all returns, v_i = lambda_i / ||lambda_i||^2
                 coef = engine.rank_weights(rewards_all, lane_lo, n) / n2
+            elif self.weighting == "top_directions":   # every return a direction of its own (lanes_per_dir = 1)
+                top = resolve_top_directions(self.top_directions, rewards_all.numel())
+                coef = engine.top_dir_weights(rewards_all, policy_reward, 1, top, lane_lo, n) / n2
             else:
                 ones = torch.ones(n, dtype=torch.int8, device=dev)
                 coef = engine.fd_weights(rewards_all, policy_reward, lane_lo, ones, n2, 1, 1.0)

@@ -106,7 +106,8 @@ class SequentialRunner(object):
                  log_to_wandb=False, wandb_project="fd-starter", wandb_group=None, wandb_run_name=None,
                  noise_table_size=25_000_000, antithetic=False, episode_len=None, device=None, verbose=True,
                  envs_per_lane=1, fp16=False, policy=None, noise_source="table", physics=False, env_shape=None,
-                 objective="reward", opt_kwargs=None, episodes_per_lane=1, common_random_numbers=False):
+                 objective="reward", opt_kwargs=None, episodes_per_lane=1, common_random_numbers=False,
+                 weighting="zscore", top_directions=None):
         """episodes_per_lane = K, common_random_numbers = False | True ("pair") | "pair" | "batch": evaluation-noise
         controls of the physics envs (Worker): every lane -- eval lanes too -- returns the mean of K episodes run in
         one launch, and the +eps / -eps lanes of a direction ("pair") or all lanes ("batch") share resets and draws.
@@ -118,7 +119,9 @@ class SequentialRunner(object):
         (episode_len, default 1000) with the matching DiscretePolicy / MujocoPolicy -- any shape the engine's
         runtime-shaped kernels take (obs_dim <= 64; act_dim <= 16 discrete, <= 8 continuous).  None: env_id.
         objective = "reward" (the reference's step) | "mixed": the learner weights every perturbation by
-        (1 - omega) z(reward) + omega z(novelty) + ent_coef z(entropy) (FiniteDifferences, build extension)."""
+        (1 - omega) z(reward) + omega z(novelty) + ent_coef z(entropy) (FiniteDifferences, build extension).
+        weighting = "zscore" (the reference's) | "centred_rank" | "top_directions", the last with top_directions = b
+        (an int >= 1, or a float fraction of the batch's directions): the learner's weighting (FiniteDifferences)."""
         if log_to_wandb:
             raise NotImplementedError("wandb logging is not part of the MI355X engine (no network)")
         self.verbose = verbose
@@ -179,7 +182,8 @@ class SequentialRunner(object):
         self.worker.want_ret_sq = self.episodes_per_lane > 1   # the within-lane spread of the epoch report
         self.learner = FiniteDifferences(self.policy, opt, self.omega, self.noise_source, noise_std=noise_std,
                                          batch_size=batch_size, ent_coef=ent_coef,
-                                         max_delayed_return=max_delayed_return, objective=objective)
+                                         max_delayed_return=max_delayed_return, objective=objective,
+                                         weighting=weighting, top_directions=top_directions)
         self.objective = objective
         self.policy_reward = 0
         self.policy_entropy = 0

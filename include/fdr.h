@@ -375,6 +375,48 @@ int fdr_fd_weights_mix(fdr_ctx* ctx, const double* rewards_all, const double* no
 int fdr_rank_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, int32_t lane_lo, int32_t n_local,
                      double* w, fdr_stream stream);
 
+/* ---- top-b direction selection (the weighting of Augmented Random Search; a build extension, the reference has
+ * no counterpart) ---------------------------------------------------------------------------------------------
+ * rewards_all holds every rank's lanes, a direction's lanes_per_dir (lpd) lanes contiguous; D = n_all / lpd.  All f64:
+ *   score  s_d = max of direction d's lpd returns, -inf when one of them is NaN
+ *   rank   rank_d = #{e : s_e > s_d, or s_e == s_d and e < d} over the GLOBAL direction indices; d is kept when
+ *          rank_d < top_dirs (stable descending order, ties to the lower index: exactly top_dirs directions)
+ *   stats  x_i = r_i - policy_reward over the top_dirs * lpd kept lanes: m their mean, sd their two-pass population
+ *          standard deviation, summed in one fixed order (thread t of 256 takes lanes t, t + 256, .., kept lanes
+ *          only; the workgroup tree of FDR_WEIGHT_ZSCORE) whatever the grid or the rank
+ *   w_i    (x_i - m) / sd on a kept lane (x_i when sd == 0, as standardize_arr), 0.0 on every other lane; a kept
+ *          NaN makes every weight NaN, as in the z-score
+ * Everything downstream -- coef_d = sum_k w_k sign_k sigma / norm2_k, the gather, NaN for an out-of-range offset
+ * (kept or not), the chunk combine, DSGD or the optimizer's apply -- is FDR_WEIGHT_CENTERED_RANK's launch, unchanged.
+ * With lpd = 2 this is ARS's sum over the kept directions of (R+ - R-) / sigma_R * delta in the engine's lambda /
+ * ||lambda||^2 normalisation; top_dirs == D reproduces FDR_WEIGHT_ZSCORE bit for bit.
+ * fdr_fd_grad_fused / fdr_fd_step / fdr_fd_step_opt refuse this mode (top_dirs does not fit their arguments);
+ * fdr_fd_grad_fused_out_len(FDR_WEIGHT_TOP_DIRS, P, n) = P.
+ * FDR_ERR_INVALID: top_dirs < 1 or > n_all / lpd, n_all % lpd != 0, lane_lo or n_local no multiple of lpd.
+ *   fdr_top_dir_weights: w [n_local] and (nullable) selected int8 [n_local / lpd] of the local lanes
+ *     [lane_lo, lane_lo + n_local); n_local == 0 returns FDR_OK and launches nothing.  workspace:
+ *     fdr_top_dir_weights_workspace_bytes(n_all) (the mask over all lanes; no counters).
+ *   fdr_fd_grad_fused_top / fdr_fd_step_top / fdr_fd_step_top_opt: fdr_fd_grad_fused / fdr_fd_step / fdr_fd_step_opt
+ *     with top_dirs in mode's place.  workspace: fdr_fd_grad_fused_top_workspace_bytes(n_dirs, lpd, P, n_all) (the
+ *     mask covers all n_all lanes); its first fdr_fd_grad_fused_counter_bytes(n_dirs, P) bytes zero before the first
+ *     call, left zero by every call. */
+#define FDR_WEIGHT_TOP_DIRS 4
+int64_t fdr_top_dir_weights_workspace_bytes(int32_t n_all);
+int fdr_top_dir_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, double policy_reward,
+                        int32_t lanes_per_dir, int32_t top_dirs, int32_t lane_lo, int32_t n_local, double* w,
+                        int8_t* selected, void* workspace, int64_t workspace_bytes, fdr_stream stream);
+int64_t fdr_fd_grad_fused_top_workspace_bytes(int32_t n_dirs, int32_t lanes_per_dir, int64_t n_params, int32_t n_all);
+int fdr_fd_grad_fused_top(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local,
+                          int32_t n_dirs, int64_t n_params, const double* rewards_all, int32_t n_all,
+                          double policy_reward, int32_t lane_lo, const int8_t* sign_local, const double* norm2_local,
+                          int32_t lanes_per_dir, float sigma, int32_t top_dirs, double* out, int64_t out_len,
+                          void* workspace, int64_t workspace_bytes, fdr_stream stream);
+int fdr_fd_step_top(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                    int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
+                    const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                    int32_t top_dirs, float* theta, double lr, double lr_scale, double* g, float* theta_hist,
+                    double* out, void* workspace, int64_t workspace_bytes, fdr_stream stream);
+
 /* ---- delayed returns: lambda with policy drift (learner/finite_differences.py:66-73, 80-114) -----
  * Return i's perturbation lambda_i = fl32(sign_i * fl32(sigma * table[idx_i + p]) + D[slot_i][p]),
  * D = drift [n_slots, P] f32 (dist_map: theta of the return's epoch minus the current theta;
@@ -469,6 +511,14 @@ int fdr_fd_step_mix_opt(fdr_ctx* ctx, const float* table, int64_t table_size, co
                         double policy_entropy, double coef_reward, double coef_novelty, double coef_entropy,
                         const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
                         float* theta, int32_t kind, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, double momentum, double dampening, int32_t nesterov, int64_t step,
+                        float* state0, float* state1, double* g, float* theta_hist, double* out, void* workspace,
+                        int64_t workspace_bytes, fdr_stream stream);
+/* fdr_fd_step_top with the optimizer's apply launch in DSGD's place (FDR_WEIGHT_TOP_DIRS above). */
+int fdr_fd_step_top_opt(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx_local, int32_t n_dirs,
+                        int64_t n_params, const double* rewards_all, int32_t n_all, double policy_reward,
+                        const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
+                        int32_t top_dirs, float* theta, int32_t kind, double lr, double beta1, double beta2, double eps,
                         double weight_decay, double momentum, double dampening, int32_t nesterov, int64_t step,
                         float* state0, float* state1, double* g, float* theta_hist, double* out, void* workspace,
                         int64_t workspace_bytes, fdr_stream stream);

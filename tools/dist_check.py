@@ -8,7 +8,8 @@
                                                                    # RCCL, one rank, the sharded exchange forced on
     ... <mode> <weighting> <out_dir> bench                         # BASELINE config 3 size (below)
 
-weighting: "zscore" (the default one-collective moments form) or "centred_rank" (all-gather + all-reduce).
+weighting: "zscore" (the default one-collective moments form), "centred_rank" or "top_directions:<b>" (b an int, or a
+fraction of the directions such as 0.25) -- the last two all-gather the returns and all-reduce g.
 The product path end to end: every rank draws the full index stream (SharedNoiseTable), Worker.evaluate runs its
 lane slice (lane_range="auto", lanes keyed by their GLOBAL index), FiniteDifferences.step exchanges and applies
 the replicated DSGD step -- for STEPS FD steps.  All ranks must end bit-identical, and equal to the
@@ -59,8 +60,10 @@ def run(mode, weighting, out, preset="small"):
     table = SharedNoiseTable(cfg["table"], policy.num_params, random_seed=124)
     agent = Agent(policy, env, random_seed=7)
     worker = Worker(policy, agent, table, None, sigma=0.02, random_seed=124)
+    from learner.finite_differences import parse_weighting
+    weighting, top = parse_weighting(weighting)
     learner = FiniteDifferences(policy, DSGD(policy.parameters(), lr=0.01), AdaptiveOmega(), table, noise_std=0.02,
-                                weighting=weighting)
+                                weighting=weighting, top_directions=top)
     # the global direction count is the 2-rank job's, whichever mode runs it
     n_dirs = 2 * cfg["dirs_per_rank"]
     upd = []

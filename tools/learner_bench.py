@@ -2,7 +2,10 @@
 one-launch fdr_fd_step, and the mixed objective's three entry points (fd_grad_fused mix, fd_step mix, fd_weights_mix
 only), and the optimizer apply launches (opt_apply_cb_kernel beside dsgd_apply_cb_kernel), at BASELINE config 3's shape
 (2048 directions x +-, P = 6092), HIP events over 50 calls (1000 for the apply launches alone).
-    python tools/learner_bench.py [n_dirs P]"""
+    python tools/learner_bench.py [n_dirs P]
+    python tools/learner_bench.py n_dirs P top     only the top-b direction section: the two weight kernels alone
+        (fdr_top_dir_weights, b = n_dirs / 4) and fd_step_top next to fd_step z-score, alternating, 5 rounds of 200 calls
+        each on the same build in the same process (e.g. 2048 6092 top; 16384 6092 top: the 8-rank direction count)"""
 import os
 import sys
 
@@ -39,6 +42,37 @@ def timeit(name, fn, n=50):
     us = e0.elapsed_time(e1) * 1e3 / n
     print("%-40s %8.2f us / call" % (name, us), flush=True)
     return us
+
+
+def top_section():
+    b = max(1, n_dirs // 4)
+    t_w = timeit("top_dir_weights (select + weights), b = D/4", lambda: engine.top_dir_weights(rew, 0.0, 2, b, 0, 2 * n_dirs),
+                 n=200)
+    t_wd = timeit("top_dir_weights, b = D", lambda: engine.top_dir_weights(rew, 0.0, 2, n_dirs, 0, 2 * n_dirs), n=200)
+    t_rk = timeit("rank_weights (centred rank, for scale)", lambda: engine.rank_weights(rew, 0, 2 * n_dirs), n=200)
+    t_g = timeit("fd_grad_fused zscore", lambda: engine.fd_grad_fused(table, idx, rew, 0.0, 0, sign, n2, 2, 0.02, P, out=g),
+                 n=200)
+    t_gt = timeit("fd_grad_fused_top", lambda: engine.fd_grad_fused_top(table, idx, rew, 0.0, 0, sign, n2, 2, 0.02, P, b,
+                                                                        out=g), n=200)
+    rounds = []
+    if P <= 65536:
+        for k in range(5):      # alternating: the shared box's drift lands on both
+            z = timeit("round %d  fd_step zscore" % k, lambda: engine.fd_step(table, idx, rew, 0.0, sign, n2, 2, 0.02, theta,
+                                                                             0.01, 0.5, g=g), n=200)
+            t = timeit("round %d  fd_step_top" % k, lambda: engine.fd_step_top(table, idx, rew, 0.0, sign, n2, 2, 0.02, theta,
+                                                                              0.01, 0.5, b, g=g), n=200)
+            rounds.append((z, t))
+        zs, ts = np.array(rounds).T
+        print("D %d P %d: fd_step zscore median %.2f us (min %.2f, max %.2f); fd_step_top median %.2f us (min %.2f, max "
+              "%.2f); difference of medians %.2f us" % (n_dirs, P, np.median(zs), zs.min(), zs.max(), np.median(ts),
+                                                        ts.min(), ts.max(), np.median(ts) - np.median(zs)))
+    print("D %d: the two top-b kernels %.2f us (b = D/4) / %.2f us (b = D), centred rank's %.2f us, next to the gradient "
+          "launch they precede, %.2f us (fd_grad_fused_top in all: %.2f us)" % (n_dirs, t_w, t_wd, t_rk, t_g, t_gt))
+
+
+if len(sys.argv) > 3 and sys.argv[3] == "top":
+    top_section()
+    sys.exit(0)
 
 
 def staged():

@@ -57,6 +57,20 @@ int context_cus(const Context& c) {
 
 static int policy_key(const fdr_policy_desc* p, PolicyKey* k) {
   if (!p) return set_error(FDR_ERR_INVALID, "policy desc is NULL");
+  k->linear = p->kind == FDR_POLICY_LINEAR;
+  if (k->linear) {  // W [n_act, n_in] alone: no hidden layer, no BN, no bias
+    if (p->hidden != 0) return set_error(FDR_ERR_INVALID, "a linear policy has hidden 0");
+    if (p->bn_mean || p->bn_var) return set_error(FDR_ERR_INVALID, "a linear policy takes no bn_mean / bn_var");
+    k->n_in = p->n_in;
+    k->n_act = p->n_act;
+    k->discrete = false;
+    k->n_params = p->n_params;
+    const int rc = linear_shape_check(*k);
+    if (rc) return rc;
+    if (p->n_params != (int64_t)p->n_act * p->n_in)
+      return set_error(FDR_ERR_INVALID, "a linear policy has n_params = n_act * n_in");
+    return FDR_OK;
+  }
   if (p->hidden != kHidden) return set_error(FDR_ERR_UNSUPPORTED, "hidden width must be 64");
   if (p->kind != FDR_POLICY_DISCRETE && p->kind != FDR_POLICY_MUJOCO)
     return set_error(FDR_ERR_INVALID, "unknown policy kind");
@@ -201,6 +215,12 @@ int fdr_policy_forward(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_la
   LanesArgs la;
   rc = lanes_args(lanes, n_lanes, k.n_params, &la);
   if (rc) return rc;
+  if (k.linear) {
+    if (!x || !out0) return set_error(FDR_ERR_INVALID, "NULL x/out");
+    if (out1) return set_error(FDR_ERR_INVALID, "a linear policy has one output: out1 must be NULL");
+    if (n_lanes == 0) return FDR_OK;
+    return launch_policy_forward_linear(k, la, n_lanes, x, out0, (hipStream_t)stream);
+  }
   if (!x || !out0 || (!k.discrete && !out1)) return set_error(FDR_ERR_INVALID, "NULL x/out");
   if (n_lanes == 0) return FDR_OK;
   return launch_policy_forward(*C, k, la, n_lanes, policy->bn_mean, policy->bn_var, x, out0, out1,
@@ -213,6 +233,8 @@ int fdr_diag_theta_prime(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_
   PolicyKey k;
   int rc = policy_key(policy, &k);
   if (rc) return rc;
+  if (k.linear)
+    return set_error(FDR_ERR_UNSUPPORTED, "no theta' read-back for a linear policy: a forward over unit vectors is one");
   LanesArgs la;
   rc = lanes_args(lanes, n_lanes, k.n_params, &la);
   if (rc) return rc;
@@ -272,6 +294,8 @@ static int rollout_args(const fdr_policy_desc* policy, const fdr_env_desc* env, 
   rc = own_checks();
   if (rc) return rc;
   const PhysicsEnv* const pe = physics_env(env->kind);
+  if (k.linear && (env->kind == FDR_ENV_SYNTH || env->kind == FDR_ENV_TRAP))
+    return set_error(FDR_ERR_UNSUPPORTED, "a linear policy runs the physics envs only");
   if (pe) {
     // the descriptor on its own first (INVALID), then the policy it is paired with (UNSUPPORTED)
     if (env->M || env->K || env->s0 || env->walkable)
@@ -280,7 +304,9 @@ static int rollout_args(const fdr_policy_desc* policy, const fdr_env_desc* env, 
     if (env->obs_dim != pe->obs || env->act_dim != pe->act)
       return set_error(FDR_ERR_INVALID, "obs_dim / act_dim are not this physics env's own");
     if (env->episode_len > 10000) return set_error(FDR_ERR_INVALID, "physics env episode_len must be 1 .. 10000");
-    if (!physics_policy_ok(*pe, k)) return set_error(FDR_ERR_UNSUPPORTED, pe->policy_msg);
+    if (k.linear && (k.n_in != pe->obs || k.n_act != pe->act))
+      return set_error(FDR_ERR_UNSUPPORTED, "a linear policy runs a physics env at the env's own (n_in, n_act)");
+    if (!k.linear && !physics_policy_ok(*pe, k)) return set_error(FDR_ERR_UNSUPPORTED, pe->policy_msg);
   }
   if (env->obs_dim != k.n_in || env->act_dim != k.n_act)
     return set_error(FDR_ERR_INVALID, "env obs/act dims do not match the policy");
@@ -350,6 +376,15 @@ int fdr_rollout_ex(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_de
     if (a.u_inject && a.os_mean)
       return set_error(FDR_ERR_UNSUPPORTED, "u_inject is not combined with the obs statistics");
   }
+  if (k.linear) {
+    if (a.u_inject) return set_error(FDR_ERR_UNSUPPORTED, "a linear policy draws nothing: no u_inject");
+    EpisodesArgs ea;
+    ea.r = a;
+    ea.n_episodes = 1;
+    ea.episode_ids = nullptr;
+    ea.ret_sq = nullptr;
+    return launch_rollout_linear(k, env->kind, ea, (hipStream_t)stream);
+  }
   return launch_rollout(*C, k, env->kind, a, (hipStream_t)stream);
 }
 
@@ -382,6 +417,7 @@ int fdr_rollout_episodes(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_
   ea.n_episodes = n_episodes;
   ea.episode_ids = episode_ids;
   ea.ret_sq = ret_sq;
+  if (k.linear) return launch_rollout_linear(k, env->kind, ea, (hipStream_t)stream);
   return launch_rollout_episodes(k, env->kind, ea, (hipStream_t)stream);
 }
 

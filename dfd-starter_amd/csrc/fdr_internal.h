@@ -36,6 +36,7 @@ struct PolicyKey {
   int n_in, n_act;
   bool discrete;
   int64_t n_params;
+  bool linear = false;  // FDR_POLICY_LINEAR: W [n_act, n_in] alone (discrete is then unused: the env decides)
 };
 
 // Device-side view of fdr_lanes_desc (passed by value as a kernel argument).
@@ -204,6 +205,14 @@ int launch_policy_forward_dyn(const PolicyKey& k, const LanesArgs& lanes, int n_
 int launch_theta_prime_dyn(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, const float* bn_mean,
                            const float* bn_var, float* out, int32_t* reads, int32_t* counted, double* n2,
                            hipStream_t stream);
+
+// FDR_POLICY_LINEAR (fdr_rollout_linear.hip): one lane per thread.  The rollout serves fdr_rollout* (n_episodes 1) and
+// fdr_rollout_episodes alike, on the physics envs at their own shapes; anything else: FDR_ERR_UNSUPPORTED, nothing
+// launched.  The forward takes any shape within linear_shape_check's limits.
+int linear_shape_check(const PolicyKey& k);
+int launch_rollout_linear(const PolicyKey& k, int env_kind, const EpisodesArgs& args, hipStream_t stream);
+int launch_policy_forward_linear(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, const float* x, float* out,
+                                 hipStream_t stream);
 
 // fdr_rollout.hip: per-lane Welford obs statistics folded into the accumulated ones (fdr_obs_stats_merge)
 int launch_obs_stats_merge(const float* mean, const float* m2, const int32_t* count, int n, int d, float* acc_mean,

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FDR_LIB", os.path.join(_HERE, "libfdr.so"))
 
 FDR_OK, FDR_ERR_INVALID, FDR_ERR_UNSUPPORTED, FDR_ERR_HIP, FDR_ERR_WORKSPACE = 0, 1, 2, 3, 4
-FDR_POLICY_DISCRETE, FDR_POLICY_MUJOCO = 0, 1
+FDR_POLICY_DISCRETE, FDR_POLICY_MUJOCO, FDR_POLICY_LINEAR = 0, 1, 2
 FDR_ENV_SYNTH, FDR_ENV_TRAP, FDR_ENV_CARTPOLE, FDR_ENV_PENDULUM = 0, 1, 2, 3
 FDR_ENV_ACROBOT, FDR_ENV_MOUNTAINCAR, FDR_ENV_MOUNTAINCAR_CONT = 4, 5, 6
 FDR_DIST_L2, FDR_DIST_TVD, FDR_DIST_W2 = 0, 1, 2

@@ -101,10 +101,12 @@ class PolicySpec(object):
     """Shape of a policy family (policies/discrete.py:34-48, policies/mujoco.py:32-41)."""
 
     def __init__(self, kind, n_in, n_act, n_params):
-        assert kind in ("discrete", "mujoco")
+        assert kind in ("discrete", "mujoco", "linear")
         self.kind, self.n_in, self.n_act, self.n_params = kind, int(n_in), int(n_act), int(n_params)
 
     def desc(self, bn_mean=None, bn_var=None):
+        if self.kind == "linear":  # W [n_act, n_in] alone: hidden 0, no BN statistics
+            return _lib.PolicyDesc(_lib.FDR_POLICY_LINEAR, self.n_in, self.n_act, 0, self.n_params, None, None)
         return _lib.PolicyDesc(_lib.FDR_POLICY_DISCRETE if self.kind == "discrete" else _lib.FDR_POLICY_MUJOCO,
                                self.n_in, self.n_act, 64, self.n_params,
                                None if bn_mean is None else bn_mean.data_ptr(),
@@ -152,12 +154,12 @@ def perturb(theta, table, idx, sign, sigma):
 
 
 def policy_forward(spec, lanes, n_lanes, x, bn_mean=None, bn_var=None, ctx=None):
-    """One observation per lane.  discrete -> probs [n, A]; mujoco -> (mean, std) [n, A]."""
+    """One observation per lane.  discrete -> probs [n, A]; mujoco -> (mean, std) [n, A]; linear -> y [n, A]."""
     _check_dev(x, bn_mean, bn_var)
     x = x.to(torch.float32).contiguous()
     dev = x.device
     out0 = torch.empty((n_lanes, spec.n_act), dtype=torch.float32, device=dev)
-    out1 = None if spec.kind == "discrete" else torch.empty_like(out0)
+    out1 = None if spec.kind in ("discrete", "linear") else torch.empty_like(out0)
     pd = spec.desc(bn_mean, bn_var)
     check(lib.fdr_policy_forward(_c(dev, ctx), ctypes.byref(pd), ctypes.byref(lanes), n_lanes, _p(x), _p(out0),
                                  _p(out1), _stream(dev)), "fdr_policy_forward")

@@ -53,7 +53,7 @@ class Policy(nn.Module):
         self._bn_layers = self._bn_modules()
         if self._bn_layers and self.KIND in ("discrete", "impala"):
             self._alias_bn(self._bn_layers)
-        if self.KIND in ("discrete", "mujoco"):
+        if self.KIND in ("discrete", "mujoco", "linear"):
             self.spec = engine.PolicySpec(self.KIND, self.input_shape, self.output_shape, self.num_params)
 
     def _bn_modules(self):

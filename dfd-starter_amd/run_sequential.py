@@ -35,7 +35,7 @@ from fdr import engine
 from envs import (AcrobotEnv, CartPoleEnv, FrameEnv, MountainCarContinuousEnv, MountainCarEnv, PendulumEnv,
                   StackedFrameEnv, SyntheticEnv, TrapEnv)
 from learner import FDBatch, FDState, FiniteDifferences
-from policies import AtariPolicy, DiscretePolicy, ImpalaPolicy, MujocoPolicy
+from policies import AtariPolicy, DiscretePolicy, ImpalaPolicy, LinearPolicy, MujocoPolicy
 from strategy import StrategyHandler
 from utils import AdaptiveOmega, SharedNoiseTable, math_helpers
 from utils.noise_sources import CounterNoiseSource, RNGNoiseSource, SimpleNoiseSource
@@ -120,10 +120,15 @@ class SequentialRunner(object):
         runtime-shaped kernels take (obs_dim <= 64; act_dim <= 16 discrete, <= 8 continuous).  None: env_id.
         objective = "reward" (the reference's step) | "mixed": the learner weights every perturbation by
         (1 - omega) z(reward) + omega z(novelty) + ent_coef z(entropy) (FiniteDifferences, build extension).
+        policy = "linear" with physics=True: a LinearPolicy of the env's shape (ARS's policy: y = W x, theta starts at
+        zero, deterministic actions) with the l2 strategy distance; every other keyword works as for the MLP policies.
         weighting = "zscore" (the reference's) | "centred_rank" | "top_directions", the last with top_directions = b
         (an int >= 1, or a float fraction of the batch's directions): the learner's weighting (FiniteDifferences)."""
         if log_to_wandb:
             raise NotImplementedError("wandb logging is not part of the MI355X engine (no network)")
+        if policy == "linear" and (not physics or env_shape is not None):
+            raise ValueError("policy='linear' runs the physics envs only: pass physics=True and one of %s"
+                             % (PHYSICS_IDS,))
         self.verbose = verbose
         self.rng = np.random.RandomState(random_seed)
         self.omega = AdaptiveOmega(default_value=omega_default_value, improvement_threshold=omega_improvement_threshold,
@@ -150,6 +155,10 @@ class SequentialRunner(object):
         elif self.frames:                              # run_sequential.py:68-71
             self.policy = ImpalaPolicy(self.env.obs_shape, self.env.act_dim, seed=random_seed, device=self.device)
             dist_fn = math_helpers.categorical_tvd
+        elif policy == "linear":                       # ARS's linear map, deterministic (policies/linear.py)
+            self.policy = LinearPolicy(self.env.obs_dim, self.env.act_dim, self.env.discrete, seed=random_seed,
+                                       device=self.device)
+            dist_fn = math_helpers.l2_dist
         elif self.env.discrete:
             self.policy = DiscretePolicy(self.env.obs_dim, self.env.act_dim, seed=random_seed, device=self.device)
             dist_fn = math_helpers.categorical_tvd

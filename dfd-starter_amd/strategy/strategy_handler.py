@@ -71,7 +71,7 @@ class StrategyHandler(object):
             frames, reward = self.zeta
             spec = engine.ImpalaSpec(p.output_shape, fp16=self.fp16, pairs=pairs)
             return engine.impala_strategies(spec, lanes_fn(1), n, frames, reward, bn_mean=bm, bn_var=bv)
-        if p.KIND != "discrete" and p.KIND != "mujoco":
+        if p.KIND not in ("discrete", "mujoco", "linear"):
             raise NotImplementedError("strategies of a %s policy" % p.KIND)
         return engine.lane_strategies(p.spec, lanes_fn, n, self.zeta, bm, bv)
 

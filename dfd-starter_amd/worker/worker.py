@@ -103,8 +103,8 @@ class Worker(object):
                 raise ValueError("episodes_per_lane / common_random_numbers need a table or counter noise source "
                                  "(host noise sources are not supported)")
             from envs import _PhysicsEnv
-            if policy.KIND not in ("discrete", "mujoco") or not isinstance(agent.env, _PhysicsEnv):
-                raise ValueError("episodes_per_lane / common_random_numbers run MLP policies on the physics envs only "
+            if policy.KIND not in ("discrete", "mujoco", "linear") or not isinstance(agent.env, _PhysicsEnv):
+                raise ValueError("episodes_per_lane / common_random_numbers run MLP and linear policies on the physics envs only "
                                  "(CartPole, Pendulum, Acrobot, MountainCar, MountainCarContinuous)")
         self.want_ret_sq = False   # launch() also asks for the lanes' sum of squared episode returns (res.reward_sq)
 
@@ -534,7 +534,7 @@ class Worker(object):
             # the stacked-frame env's frames do not depend on the actions: env 0's first n observations
             n = T if max_states is None else min(T, int(max_states))
             return engine.atari_env_frames(self.agent.env.env_seed, 0, 0, n, device=dev).cpu().numpy()
-        if p.KIND != "discrete" and p.KIND != "mujoco":
+        if p.KIND not in ("discrete", "mujoco", "linear"):
             return None
         states = torch.empty((1, T, p.input_shape), dtype=torch.float32, device=dev)
         om, osd = self.agent.obs_norm_tensors(self.fixed_obs_stats.mean, self.fixed_obs_stats.std)

@@ -38,6 +38,22 @@ typedef void* fdr_stream; /* hipStream_t */
 /* Policy families (policies/discrete.py:34-48, policies/mujoco.py:32-41). */
 #define FDR_POLICY_DISCRETE 0 /* BN-Linear-ReLU-BN-Linear-ReLU-BN-Linear-Softmax, hidden 64 */
 #define FDR_POLICY_MUJOCO 1   /* Linear-Tanh-Linear-Tanh-Linear-tanh head, hidden 64 */
+/* The linear policy of Augmented Random Search (added within fdr 0.5: one constant, no new export, no struct change).
+   Descriptor: hidden == 0, bn_mean == bn_var == NULL, n_params == n_act * n_in, else FDR_ERR_INVALID with the field
+   named; theta is W [n_act, n_in] row-major, no bias (nn.Linear(n_in, n_act, bias=False).parameters()).
+     input   x = the raw observation, or clip((s - obs_mean) / obs_std, -10, 10) with the statistics given
+     output  y_i = (((W'[i,0] x_0) + W'[i,1] x_1) + ...) in ascending j, every product and sum rounded to f32, no FMA
+     action  discrete envs (CartPole, Acrobot, MountainCar): the smallest i attaining max y; continuous envs
+             (Pendulum, MountainCarContinuous): y itself, clamped by the env as for every policy
+   The policy is deterministic: lanes->deterministic is ignored, no action draw is consumed, ent[l] = 0.0.  ret, steps,
+   norm2, the jiggle, lane_offset and the reset draws are those of the MLP policies (a lane id resets to the same state
+   bit for bit).  One lane per thread (rollout_linear_kernel).
+   Served: fdr_rollout, fdr_rollout_states, fdr_rollout_ex (states and obs statistics; u_inject is
+   FDR_ERR_UNSUPPORTED: nothing to inject) and fdr_rollout_episodes, on the five physics envs at each env's own
+   (obs, act) shape -- FDR_ENV_SYNTH, FDR_ENV_TRAP and any other shape: FDR_ERR_UNSUPPORTED, nothing launched;
+   fdr_policy_forward for 1 <= n_in <= 64, 1 <= n_act <= 16: out0 = y [n_lanes, n_act], out1 must be NULL
+   (FDR_ERR_INVALID).  fdr_diag_theta_prime is FDR_ERR_UNSUPPORTED: a forward over unit vectors reads theta' back. */
+#define FDR_POLICY_LINEAR 2
 
 /* Environments run inside the rollout kernel. */
 #define FDR_ENV_SYNTH 0 /* contractive linear-tanh system (DESIGN.md "Synthetic envs") */
@@ -46,8 +62,9 @@ typedef void* fdr_stream; /* hipStream_t */
    published classic_control formulas in f32; every lane resets to its own state, drawn from the counter
    stream by its global lane id (lane_offset + lane), so a lane's episode does not depend on the launch or shard that
    runs it.  Descriptor: M, K, s0 and walkable NULL, done_threshold 0, episode_len (the time limit) in 1 .. 10000,
-   else FDR_ERR_INVALID; a policy other than the one named here is FDR_ERR_UNSUPPORTED.  Served by fdr_rollout,
-   fdr_rollout_states and fdr_rollout_ex with every extra, always on the one-lane-per-wave kernel. */
+   else FDR_ERR_INVALID; a policy other than the one named here or FDR_POLICY_LINEAR at the env's shape is
+   FDR_ERR_UNSUPPORTED.  Served by fdr_rollout, fdr_rollout_states and fdr_rollout_ex with every extra, always on the
+   one-lane-per-wave kernel (FDR_POLICY_LINEAR: one lane per thread). */
 #define FDR_ENV_CARTPOLE 2 /* CartPole-v1: obs 4 / 2 actions, FDR_POLICY_DISCRETE; ends when the pole or cart leaves
                               its bounds (reward 1 per step taken) or at episode_len */
 #define FDR_ENV_PENDULUM 3 /* Pendulum-v1: obs 3 (cos, sin, thetadot) / 1 action dim, FDR_POLICY_MUJOCO; the action is
@@ -67,7 +84,7 @@ typedef struct fdr_policy_desc {
   int32_t kind;     /* FDR_POLICY_* */
   int32_t n_in;     /* observation size (policy.input_shape) */
   int32_t n_act;    /* discrete: number of actions; mujoco: action dims (head = 2*n_act) */
-  int32_t hidden;   /* must be 64 (hard-coded by the reference) */
+  int32_t hidden;   /* must be 64 (hard-coded by the reference); 0 for FDR_POLICY_LINEAR */
   int64_t n_params; /* P = len(get_trainable_flat()) */
   /* discrete only: eval-mode BatchNorm running stats of the 3 BN layers, concatenated
      [n_in | 64 | 64] (policies/discrete.py:38,42,46); NULL = (mean 0, var 1). */

@@ -421,6 +421,74 @@ int fdr_rollout_episodes(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_
   return launch_rollout_episodes(k, env->kind, ea, (hipStream_t)stream);
 }
 
+int fdr_rollout_runs(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_desc* env, int32_t n_runs,
+                     int32_t lanes_per_run, const float* theta_runs, const float* sigma_runs,
+                     const float* obs_mean_runs, const float* obs_std_runs, const int64_t* run_lane_offset,
+                     const float* table, int64_t table_size, const int64_t* idx, const int8_t* sign, uint64_t seed,
+                     int32_t jiggle, int32_t n_episodes, const int64_t* episode_ids, double* ret, double* ret_sq,
+                     double* ent, int32_t* steps, double* norm2, float* os_mean, float* os_m2, int32_t* os_count,
+                     float os_chance, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (!policy || !env) return set_error(FDR_ERR_INVALID, "policy / env desc is NULL");
+  if (!theta_runs || !sigma_runs || !run_lane_offset || !ret || !steps)
+    return set_error(FDR_ERR_INVALID, "NULL pointer");
+  if (n_runs < 1) return set_error(FDR_ERR_INVALID, "n_runs < 1");
+  if (lanes_per_run < 1) return set_error(FDR_ERR_INVALID, "lanes_per_run < 1");
+  if ((int64_t)n_runs * lanes_per_run > INT32_MAX)
+    return set_error(FDR_ERR_INVALID, "n_runs * lanes_per_run above 2^31 - 1");
+  if (policy->kind == FDR_POLICY_DISCRETE || policy->kind == FDR_POLICY_MUJOCO)
+    return set_error(FDR_ERR_UNSUPPORTED, "fdr_rollout_runs takes a linear policy");
+  const int32_t n_lanes = n_runs * lanes_per_run;
+  fdr_lanes_desc lanes{};
+  lanes.base = theta_runs;
+  lanes.table = table;
+  lanes.table_size = table_size;
+  lanes.idx = idx;
+  lanes.sign = sign;
+  PolicyKey k;
+  RunsArgs ra;
+  auto own_checks = [&] {
+    if (n_episodes < 1 || n_episodes > 1024) return set_error(FDR_ERR_INVALID, "n_episodes must be 1 .. 1024");
+    if ((os_mean || os_m2 || os_count) && (!os_mean || !os_m2 || !os_count))
+      return set_error(FDR_ERR_INVALID, "os_mean, os_m2 and os_count must be given together");
+    if (!physics_env(env->kind)) return set_error(FDR_ERR_UNSUPPORTED, "fdr_rollout_runs runs the physics envs only");
+    return (int)FDR_OK;
+  };
+  double ent_given = 0.0;  // rollout_args requires ent; here it is nullable
+  const int rc = rollout_args(policy, env, &lanes, n_lanes, seed, jiggle, obs_mean_runs, obs_std_runs, ret,
+                              ent ? ent : &ent_given, steps, norm2, own_checks, k, ra.e.r);
+  if (rc) return rc;
+  ra.e.r.ent = ent;
+  if (os_mean) {
+    ra.e.r.os_mean = os_mean;
+    ra.e.r.os_m2 = os_m2;
+    ra.e.r.os_count = os_count;
+    ra.e.r.os_chance = os_chance;
+  }
+  ra.e.n_episodes = n_episodes;
+  ra.e.episode_ids = episode_ids;
+  ra.e.ret_sq = ret_sq;
+  ra.theta_runs = theta_runs;
+  ra.sigma_runs = sigma_runs;
+  ra.obs_mean_runs = obs_mean_runs;
+  ra.obs_std_runs = obs_std_runs;
+  ra.run_lane_offset = run_lane_offset;
+  ra.lanes_per_run = lanes_per_run;
+  return launch_rollout_runs(k, env->kind, ra, (hipStream_t)stream);
+}
+
+int fdr_obs_stats_merge_runs(fdr_ctx* ctx, const float* mean, const float* m2, const int32_t* count, int32_t n_runs,
+                             int32_t lanes_per_run, int32_t dim, float* acc_mean, float* acc_m2, int64_t* acc_count,
+                             fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (n_runs < 1 || lanes_per_run < 1 || dim <= 0) return set_error(FDR_ERR_INVALID, "bad sizes");
+  if ((int64_t)n_runs * lanes_per_run > INT32_MAX)
+    return set_error(FDR_ERR_INVALID, "n_runs * lanes_per_run above 2^31 - 1");
+  if (!mean || !m2 || !count || !acc_mean || !acc_m2 || !acc_count) return set_error(FDR_ERR_INVALID, "NULL pointer");
+  return launch_obs_stats_merge_runs(mean, m2, count, n_runs, lanes_per_run, dim, acc_mean, acc_m2, acc_count,
+                                     (hipStream_t)stream);
+}
+
 int fdr_fd_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, double policy_reward,
                    int32_t lane_lo, int32_t n_local, const int8_t* sign_local,
                    const double* norm2_local, int32_t lanes_per_dir, float sigma, double* coef,
@@ -827,6 +895,41 @@ int fdr_fd_step_top_opt(fdr_ctx* ctx, const float* table, int64_t table_size, co
   return fd_grad_fused_impl(table, table_size, idx_local, n_dirs, n_params, rewards_all, n_all, policy_reward, 0,
                             sign_local, norm2_local, lanes_per_dir, sigma, FDR_WEIGHT_TOP_DIRS, g, theta, 0.0, 0.0,
                             theta_hist, out, workspace, workspace_bytes, stream, nullptr, &o, top_dirs);
+}
+
+int fdr_fd_step_runs(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx, const int8_t* sign,
+                     const double* norm2, const double* rewards, int64_t run_stride, int32_t n_runs, int32_t n_train,
+                     int32_t lanes_per_dir, int64_t n_params, const double* policy_reward, const float* sigma_runs,
+                     const int32_t* top_dirs, float* theta_runs, const double* lr, double lr_scale, double* g_out,
+                     double* out, fdr_stream stream) {
+  FDR_CTX(ctx, C);
+  if (!table || !idx || !sign || !norm2 || !rewards || !sigma_runs || !theta_runs || !lr || !out)
+    return set_error(FDR_ERR_INVALID, "NULL pointer");
+  if (n_runs < 1) return set_error(FDR_ERR_INVALID, "n_runs < 1");
+  if (n_train < 1 || lanes_per_dir < 1 || n_params < 1) return set_error(FDR_ERR_INVALID, "bad sizes");
+  if (n_train % lanes_per_dir != 0) return set_error(FDR_ERR_INVALID, "n_train must be a multiple of lanes_per_dir");
+  if (run_stride < n_train) return set_error(FDR_ERR_INVALID, "run_stride below n_train");
+  if (table_size < n_params) return set_error(FDR_ERR_INVALID, "table smaller than n_params");
+  FdRunsArgs a;
+  a.table = table;
+  a.max_idx = table_size - n_params;
+  a.idx = idx;
+  a.sign = sign;
+  a.norm2 = norm2;
+  a.rewards = rewards;
+  a.run_stride = run_stride;
+  a.policy_reward = policy_reward;
+  a.sigma_runs = sigma_runs;
+  a.top_dirs = top_dirs;
+  a.theta_runs = theta_runs;
+  a.lr = lr;
+  a.lr_scale = lr_scale;
+  a.g_out = g_out;
+  a.out = out;
+  a.n_dirs = n_train / lanes_per_dir;
+  a.lpd = lanes_per_dir;
+  a.P = (int)std::min<int64_t>(n_params, INT32_MAX);
+  return launch_fd_step_runs(a, n_runs, (hipStream_t)stream);
 }
 
 int fdr_rank_weights(fdr_ctx* ctx, const double* rewards_all, int32_t n_all, int32_t lane_lo, int32_t n_local,

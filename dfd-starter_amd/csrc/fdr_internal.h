@@ -214,8 +214,26 @@ int launch_rollout_linear(const PolicyKey& k, int env_kind, const EpisodesArgs& 
 int launch_policy_forward_linear(const PolicyKey& k, const LanesArgs& lanes, int n_lanes, const float* x, float* out,
                                  hipStream_t stream);
 
+// fdr_rollout_runs' kernel argument (fdr_rollout_linear.hip, rollout_runs_kernel): R runs x lanes_per_run lanes in one
+// launch, global lane g = r * lanes_per_run + l.  e holds what every lane shares (table, idx, sign, the outputs, T, key,
+// K, episode_ids; e.r.n_lanes = R * lanes_per_run); e.r.lanes.base / sigma / lane_offset and e.r.obs_mean / obs_std are
+// not read: run r's come from the arrays here.
+struct RunsArgs {
+  EpisodesArgs e;
+  const float* theta_runs;         // [R, P]
+  const float* sigma_runs;         // [R]
+  const float* obs_mean_runs;      // [R, n_in], or NULL
+  const float* obs_std_runs;       // [R, n_in], or NULL
+  const int64_t* run_lane_offset;  // [R] global id of the run's lane 0
+  int lanes_per_run;
+};
+int launch_rollout_runs(const PolicyKey& k, int env_kind, const RunsArgs& args, hipStream_t stream);
+
 // fdr_rollout.hip: per-lane Welford obs statistics folded into the accumulated ones (fdr_obs_stats_merge)
 int launch_obs_stats_merge(const float* mean, const float* m2, const int32_t* count, int n, int d, float* acc_mean,
                            float* acc_m2, int64_t* acc_count, hipStream_t stream);
+// fdr_rollout_linear.hip: run r folds its lanes_per_run partials into accumulator r (fdr_obs_stats_merge_runs)
+int launch_obs_stats_merge_runs(const float* mean, const float* m2, const int32_t* count, int n_runs, int lanes_per_run,
+                                int d, float* acc_mean, float* acc_m2, int64_t* acc_count, hipStream_t stream);
 
 }  // namespace fdr

@@ -1,5 +1,5 @@
 // Internal (non-ABI) host interface of the learner-side units behind the C ABI (fdr_api.hip): the launchers and
-// workspace queries of fdr_learner.hip, fdr_learner_fused.hip, fdr_top_dirs.hip, fdr_dsgd.hip, fdr_optim.hip, fdr_novelty.hip and
+// workspace queries of fdr_learner.hip, fdr_learner_fused.hip, fdr_top_dirs.hip, fdr_learner_runs.hip, fdr_dsgd.hip, fdr_optim.hip, fdr_novelty.hip and
 // fdr_mlp_vbn.hip, and the two structs that cross to their kernels by value (LambdaRow, FdArgs).
 #pragma once
 #include "fdr_internal.h"
@@ -134,6 +134,32 @@ int64_t fused_top_workspace_bytes(int n_dirs, int n_local, int64_t P, int n_all)
 int64_t top_dirs_workspace_bytes(int n_all);
 int launch_top_dir_weights(const double* r_all, int n_all, double pr, int lpd, int top_dirs, int lo, int n_local,
                            double* w, int8_t* selected, void* ws, int64_t ws_bytes, hipStream_t stream);
+
+// ---- fdr_learner_runs.hip ----
+// fdr_fd_step_runs: R runs, one workgroup each (fd_step_runs_kernel).  Per-lane arrays hold run_stride entries per run,
+// the first n_dirs * lpd of them the run's training lanes.  launch_fd_step_runs refuses P > kRunsMaxP and
+// n_dirs * lpd > kRunsMaxTrain (FDR_ERR_UNSUPPORTED, the limit in the message) before any launch.
+constexpr int kRunsMaxP = 32;         // parameters per run (f64 registers per thread); the physics shapes reach 18
+constexpr int kRunsMaxTrain = 4096;   // training lanes per run (the returns in LDS)
+struct FdRunsArgs {
+  const float* table;
+  int64_t max_idx;               // table_size - P: largest legal offset
+  const int64_t* idx;            // per lane; direction d of run r: idx[r * run_stride + d * lpd]
+  const int8_t* sign;            // per lane
+  const double* norm2;           // per lane
+  const double* rewards;         // per lane
+  int64_t run_stride;
+  const double* policy_reward;   // [R], or NULL: 0
+  const float* sigma_runs;       // [R]
+  const int32_t* top_dirs;       // [R], or NULL: the z-score over all lanes
+  float* theta_runs;             // [R, P], in/out
+  const double* lr;              // [R]
+  double lr_scale;
+  double* g_out;                 // [R, P], or NULL
+  double* out;                   // [R, 2]: ||d theta||, ||fl32(-g)||
+  int n_dirs, lpd, P;
+};
+int launch_fd_step_runs(const FdRunsArgs& a, int n_runs, hipStream_t stream);
 
 // ---- fdr_dsgd.hip ----
 int64_t dsgd_workspace_bytes(int64_t P);

@@ -181,6 +181,166 @@ __global__ __launch_bounds__(kLinearBlock) void rollout_linear_kernel(EpisodesAr
   }
 }
 
+// ---- run batches (fdr_rollout_runs): R runs x L lanes in one launch ---------------------------------------------
+// rollout_runs_kernel is rollout_linear_kernel with the lane's theta, sigma, observation statistics and global id
+// taken from the lane's RUN: thread g of the grid is lane g % L of run g / L, whatever the wave and workgroup
+// boundaries; idx, sign, episode_ids and every output stay indexed by g.  The episode loop below repeats
+// rollout_linear_kernel's text: moved into one shared __forceinline__ body, the 40 solo instances kept their
+// instruction counts but not their register allocation (tools/isa_diff.py; DESIGN.md 3.1.4 has the diff), so the solo
+// kernel stays as it was and this one holds a copy.  A change to one episode loop belongs in both:
+// tests/test_gpu_runs.py holds the two bit-equal.
+template <int P, int NIN>
+struct RunLane {
+  const RunsArgs& ra;
+  int run;
+  __device__ __forceinline__ ParamSrc src(int lane) const {
+    LanesArgs l = ra.e.r.lanes;
+    l.base = ra.theta_runs + (int64_t)run * P;
+    l.base_stride = 0;
+    l.sigma = ra.sigma_runs[run];
+    return l.src(lane);
+  }
+  __device__ __forceinline__ const float* obs_mean() const { return ra.obs_mean_runs + (int64_t)run * NIN; }
+  __device__ __forceinline__ const float* obs_std() const { return ra.obs_std_runs + (int64_t)run * NIN; }
+  __device__ __forceinline__ uint64_t glane(int lane) const {
+    return (uint64_t)(ra.run_lane_offset[run] + (int64_t)(lane - run * ra.lanes_per_run));
+  }
+};
+
+// FEAT: a subset of kFeatObsStats | kFeatObsNorm (no state recording).
+template <int ENV, int FEAT>
+__global__ __launch_bounds__(kLinearBlock) void rollout_runs_kernel(RunsArgs ra) {
+  static_assert((FEAT & ~(kFeatObsNorm | kFeatObsStats)) == 0, "runs: obs-norm and obs-stats only");
+  using E = PhysicsSpec<ENV>;
+  constexpr int NIN = E::NIN, NA = E::NA, P = NIN * NA;
+  const EpisodesArgs& ea = ra.e;
+  const RolloutArgs& a = ea.r;
+  const int lane = blockIdx.x * kLinearBlock + threadIdx.x;
+  if (lane >= a.n_lanes) return;
+  const RunLane<P, NIN> from{ra, lane / ra.lanes_per_run};
+
+  // theta' and the lane's norm2 (f64, ascending p); an out-of-range offset never reaches the table (LanesArgs::src)
+  ParamSrc src = from.src(lane);
+  float w[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) w[p] = src.get(p);
+  if (a.norm2) a.norm2[lane] = src.n2;
+
+  [[maybe_unused]] float om[NIN], osd[NIN];
+  if constexpr (FEAT & kFeatObsNorm) {
+#pragma unroll
+    for (int j = 0; j < NIN; ++j) {
+      om[j] = from.obs_mean()[j];
+      osd[j] = from.obs_std()[j];
+    }
+  }
+
+  const int T = a.T, K = ea.n_episodes;
+  const uint64_t key = a.key;
+  const uint64_t glane = from.glane(lane);  // physical global lane: the jiggle's key
+  double rsum = 0.0, rsq = 0.0;
+  int nsum = 0;
+  // the lane's Welford statistic, running on across its episodes (ObsWelford's arithmetic per element)
+  [[maybe_unused]] int os_n = 0;
+  [[maybe_unused]] float os_mean[NIN], os_m2[NIN];
+#pragma unroll
+  for (int j = 0; j < NIN; ++j) os_mean[j] = os_m2[j] = 0.f;
+
+  for (int ep = 0; ep < K; ++ep) {
+    const uint64_t ulane =
+        ea.episode_ids ? (uint64_t)ea.episode_ids[(int64_t)lane * K + ep] : glane * (uint64_t)K + (uint64_t)ep;
+    LinearSim<ENV> env;
+    env.sim.reset(key, ulane);
+    double racc = 0.0;
+    int nsteps = T;
+    bool done = false;
+    for (int t = 0; t < T; ++t) {
+      if (!done) {  // a finished thread adds nothing and stores nothing more
+        float s[NIN];
+        env.obs(s);
+        if constexpr (FEAT & kFeatObsStats) {
+          // the coin of step t of stream ulane: the one the wave-per-lane kernels draw 64 steps at a time
+          if (uniform24(hash_ctr(key, ulane, (uint64_t)t, 14)) < a.os_chance) {
+#pragma clang fp contract(off)
+            const int cc = os_n;
+            os_n += 1;
+#pragma unroll
+            for (int j = 0; j < NIN; ++j) {
+              const float delta = s[j] - os_mean[j];
+              const float delta_n = delta / (float)os_n;
+              os_mean[j] += delta_n;
+              os_m2[j] += (delta * delta_n) * (float)cc;
+            }
+          }
+        }
+        if constexpr (FEAT & kFeatObsNorm) {
+#pragma unroll
+          for (int j = 0; j < NIN; ++j) s[j] = fminf(fmaxf((s[j] - om[j]) / osd[j], -10.f), 10.f);
+        }
+        float y[NA];
+#pragma unroll
+        for (int i = 0; i < NA; ++i) y[i] = linear_row<NIN>(w + i * NIN, s);
+        if (env.step(y, racc)) {
+          done = true;
+          nsteps = t + 1;
+        }
+      }
+      if (__ballot(!done) == 0) break;  // the wave leaves when all its threads are done
+    }
+    // fold the episode into the lane totals (sequential f64, episode order)
+    rsum += racc;
+    rsq += racc * racc;
+    nsum += nsteps;
+  }
+
+  double r = rsum / (double)K;
+  if (a.jiggle) r += (hash_ctr(key, glane, kJiggleT, 15) & 1ull) ? 1e-12 : -1e-12;
+  a.ret[lane] = r;
+  if (a.ent) a.ent[lane] = 0.0;  // a deterministic policy
+  a.steps[lane] = nsum;
+  if (ea.ret_sq) ea.ret_sq[lane] = rsq;
+  if constexpr (FEAT & kFeatObsStats) {
+#pragma unroll
+    for (int j = 0; j < NIN; ++j) {
+      a.os_mean[(int64_t)lane * NIN + j] = os_mean[j];
+      a.os_m2[(int64_t)lane * NIN + j] = os_m2[j];
+    }
+    a.os_count[lane] = os_n;
+  }
+}
+
+// obs_stats_merge_kernel (fdr_rollout.hip) per run: workgroup r folds run r's L partials into accumulator r in lane
+// order, one thread per observation dimension, the same f32 expressions.
+__global__ void obs_stats_merge_runs_kernel(const float* __restrict__ mean, const float* __restrict__ m2,
+                                            const int32_t* __restrict__ count, int L, int d, float* acc_mean,
+                                            float* acc_m2, int64_t* acc_count) {
+#pragma clang fp contract(off)
+  const int j = threadIdx.x, r = blockIdx.x;
+  const int64_t l0 = (int64_t)r * L;
+  int64_t c = acc_count[r];
+  float m = j < d ? acc_mean[(int64_t)r * d + j] : 0.f, v = j < d ? acc_m2[(int64_t)r * d + j] : 0.f;
+  for (int i = 0; i < L; ++i) {
+    const int64_t oc = count[l0 + i];
+    if (oc == 0) continue;
+    const int64_t cnt = c + oc;
+    if (j < d) {
+      const float om = mean[(l0 + i) * d + j], ov = m2[(l0 + i) * d + j];
+      const float md = om - m;
+      const float mds = md * md;
+      const float cm = ((float)c * m + (float)oc * om) / (float)cnt;
+      v = (v + ov) + ((mds * (float)c) * (float)oc) / (float)cnt;
+      m = cm;
+    }
+    c = cnt;
+  }
+  if (j < d) {
+    acc_mean[(int64_t)r * d + j] = m;
+    acc_m2[(int64_t)r * d + j] = v;
+  }
+  __syncthreads();  // every thread has read acc_count[r]
+  if (j == 0) acc_count[r] = c;
+}
+
 // out[l, i] = row i of theta'_l against x[l, :], any n_in <= 64 / n_act <= 16
 __global__ __launch_bounds__(kLinearBlock) void policy_forward_linear_kernel(LanesArgs lanes, int n_lanes, int n_in,
                                                                             int n_act, const float* x, float* out) {
@@ -235,6 +395,37 @@ int launch_rollout_linear(const PolicyKey& k, int env_kind, const EpisodesArgs& 
              : set_error(FDR_ERR_UNSUPPORTED, "a linear policy takes no injected draws");
   });
   return rc;
+}
+
+constexpr int kRunsFeatBits = kFeatObsStats | kFeatObsNorm;  // 4 sets per env
+
+int launch_rollout_runs(const PolicyKey& k, int env_kind, const RunsArgs& args, hipStream_t stream) {
+  const PhysicsEnv* const pe = physics_env(env_kind);
+  if (!pe) return set_error(FDR_ERR_UNSUPPORTED, "a linear policy runs the physics envs only");
+  if (!k.linear) return set_error(FDR_ERR_UNSUPPORTED, "fdr_rollout_runs takes a linear policy");
+  if (k.n_in != pe->obs || k.n_act != pe->act)
+    return set_error(FDR_ERR_UNSUPPORTED, "a linear policy runs a physics env at the env's own (obs, act) shape");
+  const int feat = rollout_feat(args.e.r, false);
+  const dim3 grid((args.e.r.n_lanes + kLinearBlock - 1) / kLinearBlock), block(kLinearBlock);
+  int rc = FDR_OK;
+  with_physics_env(env_kind, [&](auto spec) {  // pe: env_kind is one of them
+    using E = decltype(spec);
+    const bool hit = launch_feat_set<kRunsFeatBits>(feat, [&](auto f) {
+      hipLaunchKernelGGL((rollout_runs_kernel<E::ENV, decltype(f)::value>), grid, block, 0, stream, args);
+    });
+    rc = hit ? check_launch("rollout_runs_kernel")
+             : set_error(FDR_ERR_UNSUPPORTED, "fdr_rollout_runs takes no state recording or injected draws");
+  });
+  return rc;
+}
+
+int launch_obs_stats_merge_runs(const float* mean, const float* m2, const int32_t* count, int n_runs, int lanes_per_run,
+                                int d, float* acc_mean, float* acc_m2, int64_t* acc_count, hipStream_t stream) {
+  if (d > 1024) return set_error(FDR_ERR_UNSUPPORTED, "obs_dim > 1024");
+  const int threads = (d + 63) / 64 * 64;
+  hipLaunchKernelGGL(obs_stats_merge_runs_kernel, dim3(n_runs), dim3(threads), 0, stream, mean, m2, count,
+                     lanes_per_run, d, acc_mean, acc_m2, acc_count);
+  return check_launch("obs_stats_merge_runs_kernel");
 }
 
 }  // namespace fdr

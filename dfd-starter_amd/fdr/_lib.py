@@ -43,7 +43,8 @@ EXPORTS = ("fdr_version", "fdr_last_error", "fdr_ctx_create", "fdr_ctx_destroy",
            "fdr_diag_theta_prime", "fdr_fd_grad_fused_mix", "fdr_fd_step_mix", "fdr_fd_weights_mix",
            "fdr_opt_workspace_bytes", "fdr_opt_step", "fdr_fd_step_opt", "fdr_fd_step_mix_opt", "fdr_noise_fill",
            "fdr_rollout_episodes", "fdr_top_dir_weights_workspace_bytes", "fdr_top_dir_weights",
-           "fdr_fd_grad_fused_top_workspace_bytes", "fdr_fd_grad_fused_top", "fdr_fd_step_top", "fdr_fd_step_top_opt")
+           "fdr_fd_grad_fused_top_workspace_bytes", "fdr_fd_grad_fused_top", "fdr_fd_step_top", "fdr_fd_step_top_opt",
+           "fdr_rollout_runs", "fdr_obs_stats_merge_runs", "fdr_fd_step_runs")
 
 
 class FDRError(RuntimeError):
@@ -116,6 +117,12 @@ def _load():
                                                 ctypes.POINTER(LanesDesc), I32, U64, I32, P, P, I32, P, P, P, P, P, P,
                                                 P, P, P, F32, P]),
         "fdr_obs_stats_merge": (ctypes.c_int, [P, P, P, P, I32, I32, P, P, P, P]),
+        # run batches: R linear-policy runs per launch
+        "fdr_rollout_runs": (ctypes.c_int, [P, ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc), I32, I32, P, P, P,
+                                            P, P, P, I64, P, P, U64, I32, I32, P, P, P, P, P, P, P, P, P, F32, P]),
+        "fdr_obs_stats_merge_runs": (ctypes.c_int, [P, P, P, P, I32, I32, I32, P, P, P, P]),
+        "fdr_fd_step_runs": (ctypes.c_int, [P, P, I64, P, P, P, P, I64, I32, I32, I32, I64, P, P, P, P, P, F64, P, P,
+                                            P]),
         "fdr_noise_draw_indices": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_int32), I64, I32, P]),
         "fdr_noise_fill": (ctypes.c_int, [P, U64, P, U64, I64, I32, I64, P, P]),
         "fdr_fd_lambda_norms": (ctypes.c_int, [P, P, I64, P, P, P, I32, I64, F32, P, I32, P, P]),

@@ -887,6 +887,110 @@ def obs_stats_merge(mean, m2, count, acc_mean, acc_m2, acc_count):
                                   _stream(mean.device)), "fdr_obs_stats_merge")
 
 
+# ---- run batches: R independent linear-policy runs per launch (run_population.py) ------------------
+def _runs_f32(t, shape, what):
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be contiguous float32 %s" % (what, list(shape)))
+
+
+def rollout_runs(spec, env, theta_runs, sigma_runs, run_lane_offset, lanes_per_run, seed, table=None, idx=None,
+                 sign=None, n_episodes=1, episode_ids=None, jiggle=True, obs_mean_runs=None, obs_std_runs=None,
+                 obs_stats=None, ret_sq=False, out=None, ctx=None):
+    """fdr_rollout_runs: R runs x lanes_per_run lanes of a linear policy in one launch.  theta_runs [R, P], sigma_runs
+    [R], obs_mean_runs / obs_std_runs [R, n_in] (both or neither) f32 and run_lane_offset [R] i64 per run; idx / sign
+    [R * L] into the shared table and episode_ids [R * L, K] per lane.  Run r's lanes are bit for bit
+    rollout_episodes' for run r's slices.  -> RolloutResult over the R * L lanes (entropy 0.0), as rollout_episodes."""
+    _check_dev(theta_runs, sigma_runs, run_lane_offset, table, idx, sign, episode_ids, obs_mean_runs, obs_std_runs)
+    dev = theta_runs.device
+    R, L, K = theta_runs.shape[0], int(lanes_per_run), int(n_episodes)
+    n_lanes = R * L
+    _runs_f32(theta_runs, (R, spec.n_params), "theta_runs")
+    _runs_f32(sigma_runs, (R,), "sigma_runs")
+    if run_lane_offset.dtype != torch.int64 or not run_lane_offset.is_contiguous() or run_lane_offset.numel() != R:
+        raise ValueError("run_lane_offset must be contiguous int64 [R]")
+    if (obs_mean_runs is None) != (obs_std_runs is None):
+        raise ValueError("obs_mean_runs and obs_std_runs go together")
+    if obs_mean_runs is not None:
+        _runs_f32(obs_mean_runs, (R, spec.n_in), "obs_mean_runs")
+        _runs_f32(obs_std_runs, (R, spec.n_in), "obs_std_runs")
+    if table is not None:
+        if idx is None or idx.dtype != torch.int64 or not idx.is_contiguous() or idx.numel() != n_lanes:
+            raise ValueError("idx must be contiguous int64 [R * lanes_per_run]")
+        if sign is not None and (sign.dtype != torch.int8 or not sign.is_contiguous() or sign.numel() != n_lanes):
+            raise ValueError("sign must be contiguous int8 [R * lanes_per_run]")
+    if episode_ids is not None and (episode_ids.dtype != torch.int64 or not episode_ids.is_contiguous() or
+                                    episode_ids.numel() != n_lanes * K):
+        raise ValueError("episode_ids must be contiguous int64 [R * lanes_per_run, n_episodes]")
+    if out is None:
+        out = _rollout_outputs(n_lanes, dev)
+    sq = None
+    if ret_sq:
+        sq = getattr(out, "reward_sq", None)
+        if sq is None:
+            sq = out.reward_sq = torch.empty(n_lanes, dtype=torch.float64, device=dev)
+    om = m2 = cnt = None
+    chance = 0.0
+    if obs_stats is not None:
+        chance = float(obs_stats)
+        om, m2, cnt = (getattr(out, "obs_mean", None), getattr(out, "obs_m2", None), getattr(out, "obs_count", None))
+        if om is None:
+            om, m2, cnt = _obs_stat_outputs(out, n_lanes, spec.n_in, dev)
+    pd = spec.desc()
+    ed = env.desc()
+    check(lib.fdr_rollout_runs(_c(dev, ctx), ctypes.byref(pd), ctypes.byref(ed), R, L, _p(theta_runs), _p(sigma_runs),
+                               _p(obs_mean_runs), _p(obs_std_runs), _p(run_lane_offset), _p(table),
+                               0 if table is None else table.numel(), _p(idx), _p(sign),
+                               ctypes.c_uint64(seed & ((1 << 64) - 1)), 1 if jiggle else 0, K, _p(episode_ids),
+                               _p(out.reward), _p(sq), _p(out.entropy), _p(out.timesteps), _p(out.norm2), _p(om), _p(m2),
+                               _p(cnt), chance, _stream(dev)), "fdr_rollout_runs")
+    return out
+
+
+def obs_stats_merge_runs(mean, m2, count, lanes_per_run, acc_mean, acc_m2, acc_count):
+    """fdr_obs_stats_merge_runs: run r folds its lanes_per_run partials (mean / m2 [R * L, dim], count [R * L]) into
+    accumulator r (acc_mean / acc_m2 [R, dim] f32, acc_count [R] i64) in lane order, in place, one launch."""
+    _check_dev(mean, m2, count, acc_mean, acc_m2, acc_count)
+    R, d = acc_mean.shape
+    L = int(lanes_per_run)
+    if mean.shape[0] != R * L or mean.shape[1] != d or count.numel() != R * L or acc_count.numel() != R:
+        raise ValueError("obs_stats_merge_runs: shapes do not match [R * L, dim] / [R, dim]")
+    check(lib.fdr_obs_stats_merge_runs(_c(mean.device), _p(mean), _p(m2), _p(count), R, L, d, _p(acc_mean), _p(acc_m2),
+                                       _p(acc_count), _stream(mean.device)), "fdr_obs_stats_merge_runs")
+
+
+def fd_step_runs(table, idx, sign, norm2, rewards, run_stride, n_train, lanes_per_dir, sigma_runs, theta_runs, lr,
+                 lr_scale, policy_reward=None, top_dirs=None, g=None, out=None):
+    """fdr_fd_step_runs: the whole FD step (top-b or z-score weights, gradient, DSGD) of R runs in one launch, one
+    workgroup per run.  idx / sign / norm2 / rewards: per lane, run_stride entries per run, the first n_train of them
+    the run's training lanes.  sigma_runs f32, lr f64, policy_reward f64 (None: 0), top_dirs i32 (None: z-score over
+    all lanes): [R] device tensors.  theta_runs [R, P] is stepped in place.  -> out f64 [R, 2] = (||d theta||, ||grad||);
+    g: None or f64 [R, P] receiving the gradients."""
+    _check_dev(table, idx, sign, norm2, rewards, sigma_runs, theta_runs, lr, policy_reward, top_dirs, g, out)
+    dev = theta_runs.device
+    R, P = theta_runs.shape
+    for t, dt, what in ((idx, torch.int64, "idx"), (sign, torch.int8, "sign"), (norm2, torch.float64, "norm2"),
+                        (rewards, torch.float64, "rewards")):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < (R - 1) * int(run_stride) + int(n_train):
+            raise ValueError("%s must be contiguous %s with run_stride entries per run" % (what, dt))
+    _runs_f32(theta_runs, (R, P), "theta_runs")
+    _runs_f32(sigma_runs, (R,), "sigma_runs")
+    for t, dt, what in ((lr, torch.float64, "lr"), (policy_reward, torch.float64, "policy_reward"),
+                        (top_dirs, torch.int32, "top_dirs")):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() != R):
+            raise ValueError("%s must be contiguous %s [R]" % (what, dt))
+    if g is not None and (g.dtype != torch.float64 or not g.is_contiguous() or g.numel() != R * P):
+        raise ValueError("g must be contiguous float64 [R, P]")
+    if out is None:
+        out = torch.empty((R, 2), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * R:
+        raise ValueError("out must be contiguous float64 [R, 2]")
+    check(lib.fdr_fd_step_runs(_c(dev), _p(table), table.numel(), _p(idx), _p(sign), _p(norm2), _p(rewards),
+                               int(run_stride), R, int(n_train), int(lanes_per_dir), P, _p(policy_reward),
+                               _p(sigma_runs), _p(top_dirs), _p(theta_runs), _p(lr), float(lr_scale), _p(g), _p(out),
+                               _stream(dev)), "fdr_fd_step_runs")
+    return out
+
+
 # ---- counter-based noise rows (utils/noise_sources.py CounterNoiseSource) --------------------------
 def noise_fill(seed, n_rows, n_params, row_stride=None, ids=None, first_id=0, out=None, device=None):
     """out [n_rows * row_stride] f32: row r = the normals of direction id ids[r] (device int64 / uint64 bits, [n_rows])

@@ -133,7 +133,7 @@ typedef struct fdr_lanes_desc {
  * contexts -- on one device or on two -- are independent.  ctx = NULL selects the process-wide default context
  * (device-agnostic; FDR_ROLLOUT in the environment sets its initial rollout selection, and new contexts copy it). */
 const char* fdr_version(void); /* "fdr 0.5 gfx950" (0.5: fdr_impala_bn_refresh, fdr_atari_bn_refresh, fdr_atari_strategies,
-                                  fdr_noise_fill; 0.4:
+                                  fdr_noise_fill, the run-batch entries; 0.4:
                                   fdr_env_desc.done_threshold / done_dim) */
 const char* fdr_last_error(void);
 typedef struct fdr_ctx fdr_ctx;
@@ -257,6 +257,30 @@ int fdr_rollout_episodes(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_
                          double* ret, double* ret_sq, double* ent, int32_t* steps, double* norm2, float* os_mean,
                          float* os_m2, int32_t* os_count, float os_chance, fdr_stream stream);
 
+/* ---- run batches: R independent linear-policy runs x L lanes in ONE launch (added within fdr 0.5: three exports,
+ * no struct: fdr_rollout_runs, fdr_obs_stats_merge_runs, fdr_fd_step_runs) ----------------------------------------
+ * FDR_POLICY_LINEAR on the five physics envs at the env's own shape (any other policy kind, env kind or shape:
+ * FDR_ERR_UNSUPPORTED, nothing launched).  Global lane g = r * lanes_per_run + l is lane l of run r = g / lanes_per_run,
+ * whatever the wave and workgroup boundaries.  Per run (device arrays):
+ *   theta_runs [R, P] f32, sigma_runs [R] f32, obs_mean_runs / obs_std_runs [R, n_in] f32 (both NULL or both set),
+ *   run_lane_offset [R] i64: the global id of the run's lane 0.
+ * Per lane, over all R * L lanes: idx / sign into the one shared table (table NULL: every lane unperturbed),
+ * episode_ids [R * L, K] (nullable).  Outputs over the R * L lanes as fdr_rollout_episodes has them; ent is nullable
+ * and is written 0.0 (a linear policy is deterministic).
+ * DEFINITION: run r's L lanes are, bit for bit in every output, what fdr_rollout_episodes writes when called with
+ * base = theta_runs + r * P, base_stride = 0, the same table and run r's slices of idx and sign, sigma = sigma_runs[r],
+ * lane_offset = run_lane_offset[r], run r's rows of obs_mean_runs / obs_std_runs, run r's slice of episode_ids and the
+ * same seed, jiggle, n_episodes and os_chance.  An out-of-range idx is never dereferenced: that lane runs unperturbed
+ * with norm2 = NaN.  FDR_ERR_INVALID: a NULL required pointer, n_runs < 1, lanes_per_run < 1, n_runs * lanes_per_run
+ * above 2^31 - 1, n_episodes outside 1 .. 1024, and fdr_rollout_episodes' descriptor refusals. */
+int fdr_rollout_runs(fdr_ctx* ctx, const fdr_policy_desc* policy, const fdr_env_desc* env, int32_t n_runs,
+                     int32_t lanes_per_run, const float* theta_runs, const float* sigma_runs,
+                     const float* obs_mean_runs, const float* obs_std_runs, const int64_t* run_lane_offset,
+                     const float* table, int64_t table_size, const int64_t* idx, const int8_t* sign, uint64_t seed,
+                     int32_t jiggle, int32_t n_episodes, const int64_t* episode_ids, double* ret, double* ret_sq,
+                     double* ent, int32_t* steps, double* norm2, float* os_mean, float* os_m2, int32_t* os_count,
+                     float os_chance, fdr_stream stream);
+
 /* ---- noise-table index draw on the HOST (utils/noise_sources.py:44-47) -----------------------------
  * out[i], i < n: the indices n successive RandomState.randint(0, max_idx) calls return, drawn from the MT19937
  * state key [624] u32 / *pos (numpy RandomState.get_state()[1:3]) and advanced in place: 32-bit words masked by
@@ -286,6 +310,13 @@ int fdr_noise_fill(fdr_ctx* ctx, uint64_t seed, const uint64_t* ids, uint64_t fi
  * in/out) in index order with the reference's f32 formulas; zero-count partials are skipped. */
 int fdr_obs_stats_merge(fdr_ctx* ctx, const float* mean, const float* m2, const int32_t* count, int32_t n, int32_t dim,
                         float* acc_mean, float* acc_m2, int64_t* acc_count, fdr_stream stream);
+
+/* fdr_obs_stats_merge for R runs in one launch: mean / m2 [R * L, dim], count [R * L]; acc_mean / acc_m2 [R, dim] f32
+ * and acc_count [R] i64, in/out.  Run r folds its L = lanes_per_run partials in lane order into accumulator r: bit for
+ * bit fdr_obs_stats_merge over run r's slices (a run whose partials all have count 0 is left unchanged). */
+int fdr_obs_stats_merge_runs(fdr_ctx* ctx, const float* mean, const float* m2, const int32_t* count, int32_t n_runs,
+                             int32_t lanes_per_run, int32_t dim, float* acc_mean, float* acc_m2, int64_t* acc_count,
+                             fdr_stream stream);
 
 /* ---- FD weighting (learner/finite_differences.py:40-49, utils/math_helpers.py:127-134) --
  * z = standardize(rewards_all - policy_reward) over ALL n_all lanes (f64, population std,
@@ -433,6 +464,27 @@ int fdr_fd_step_top(fdr_ctx* ctx, const float* table, int64_t table_size, const 
                     const int8_t* sign_local, const double* norm2_local, int32_t lanes_per_dir, float sigma,
                     int32_t top_dirs, float* theta, double lr, double lr_scale, double* g, float* theta_hist,
                     double* out, void* workspace, int64_t workspace_bytes, fdr_stream stream);
+
+/* ---- the whole FD step of R independent runs in ONE launch (run batches; one 256-thread workgroup per run) ------
+ * idx, sign, norm2, rewards: per lane, run_stride entries from one run to the next; the first n_train = D * lpd entries
+ * of a run are its training lanes (a direction's lanes_per_dir lanes contiguous), whatever lies behind them (the
+ * run's eval lanes) is never read.  Per run r: policy_reward [R] f64 (NULL: 0), sigma_runs [R] f32, top_dirs [R] i32
+ * (NULL: the z-score over all lanes), theta_runs [R, P] f32 in/out, lr [R] f64; lr_scale is shared.
+ * Per run the formulas are FDR_WEIGHT_TOP_DIRS' above (scores, the stable selection with ties to the lower index,
+ * two-pass statistics over the kept lanes, w), coef_d = sum_k w_k sign_k sigma / norm2_k over the lanes with
+ * sign != 0, g[p] = sum_d coef_d * table[idx_d + p] in f64 (NaN for an out-of-range offset, kept or not) and
+ * fdr_dsgd_step on fl32(-g): a zero or NaN norm leaves theta untouched with out = [0, norm].
+ * top_dirs[r] outside 1 .. D is a device value and cannot be refused here: it makes run r's weights NaN, hence g NaN,
+ * theta untouched, out = [0, NaN]; the other runs are not affected.  top_dirs[r] == D equals the NULL form bit for bit.
+ * Every summation order depends on the run's own (D, lpd, P) alone: a run's bits depend neither on R nor on its
+ * position.  g_out [R, P] f64 (nullable); out [R, 2] f64 = (||d theta||, ||grad||).  No workspace, no counters.
+ * FDR_ERR_UNSUPPORTED, the limit named in fdr_last_error(): n_params > 32; n_train > 4096.
+ * FDR_ERR_INVALID: n_train % lanes_per_dir != 0, run_stride < n_train, n_runs < 1, a NULL required pointer. */
+int fdr_fd_step_runs(fdr_ctx* ctx, const float* table, int64_t table_size, const int64_t* idx, const int8_t* sign,
+                     const double* norm2, const double* rewards, int64_t run_stride, int32_t n_runs, int32_t n_train,
+                     int32_t lanes_per_dir, int64_t n_params, const double* policy_reward, const float* sigma_runs,
+                     const int32_t* top_dirs, float* theta_runs, const double* lr, double lr_scale, double* g_out,
+                     double* out, fdr_stream stream);
 
 /* ---- delayed returns: lambda with policy drift (learner/finite_differences.py:66-73, 80-114) -----
  * Return i's perturbation lambda_i = fl32(sign_i * fl32(sigma * table[idx_i + p]) + D[slot_i][p]),

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import branch_cases as bc
 import linear_cases as lc
 import linear_ref as lref
 import physics_ref as ref
@@ -280,7 +281,8 @@ def _step_candidates(env, cur, acts):
 def test_per_step_consistency(eng, name):
     """Along the GPU's own recorded trajectory: y recomputed from recorded state t gives the action; the transition to
     recorded state t + 1 matches the f32 restatement under THAT action within the env's existing one-step tolerance,
-    and (discrete envs) under no other action unless the candidates coincide; nothing is written after the last step."""
+    and (discrete envs) under no other action unless the candidates coincide; nothing is written after the last step
+    and no recorded state is one the env ends an episode on."""
     c = lc.case(name)
     g = _recorded(eng, name)
     S, steps = g["states"], g["steps"]
@@ -289,6 +291,9 @@ def test_per_step_consistency(eng, name):
     assert steps.min() >= 1 and steps.max() <= c.T
     for l, n in enumerate(steps):
         assert np.all(np.isfinite(S[l, :n])) and np.all(np.isnan(S[l, n:])), "lane %d wrote after its last step" % l
+    # no recorded state is terminal: a lane that should have stopped and went on would record one
+    rec = np.concatenate([S[l, :n] for l, n in enumerate(steps)])
+    assert not bc.terminal_recorded(c.env, rec).any(), "a lane went on from a terminal state"
     ll, tt = _transitions(steps)
     cur, nxt = S[ll, tt], S[ll, tt + 1]
     y = lref.dot_ordered(Wm[ll], lref.normalise(cur, c.obs_mean, c.obs_std))

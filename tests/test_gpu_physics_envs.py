@@ -351,7 +351,7 @@ def test_pendulum(eng):
     assert np.all(np.abs(S[..., 2]) <= 8)
     # one-step consistency and the return, along the GPU's own trajectory
     thetas = onoise.perturb(theta, tab.table, idx, sign, SIGMA)
-    worst, n_checked = 0.0, 0
+    worst, n_checked, beyond = 0.0, 0, np.zeros(2, np.int64)
     for l in range(L):
         obs = S[l]
         mean, std = opol.lanes_forward("mujoco", 3, 1, np.broadcast_to(thetas[l], (T, theta.size)), obs)
@@ -366,10 +366,14 @@ def test_pendulum(eng):
         err = np.abs(want[:-1] - obs[1:]).max(axis=-1)
         worst = max(worst, float(err[ok].max()))
         n_checked += int(ok.sum())
+        beyond += [int((a > 2.0).sum()), int((a < -2.0).sum())]
         assert np.all(err[ok] <= 5e-6), "lane %d: max one-step error %.3g" % (l, err[ok].max())
         assert abs(g["ret"][l] - rew.astype(np.float64).sum()) <= 4e-3, \
             "lane %d: ret %.6f, restated %.6f" % (l, g["ret"][l], rew.astype(np.float64).sum())
     print("pendulum one-step: %d transitions, max |gpu - restated| = %.3g" % (n_checked, worst))
+    # the census of tests/branch_cases.py for this launch (printed, not required: the sampled noise decides)
+    print("pendulum branches: torque beyond +2 / -2 at %d / %d steps, speed at +8 / -8 in %d / %d recorded states"
+          % (beyond[0], beyond[1], int((S[..., 2] == 8).sum()), int((S[..., 2] == -8).sum())))
     assert n_checked > 0.9 * L * (T - 1)
     assert len(np.unique(np.round(g["ret"], 3))) > 40       # every lane its own episode
 
